@@ -1,20 +1,33 @@
 """KGDet R50-FPN benchmark on MI355X (contract: see the task statement / DESIGN.md).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]   (N > 1: launched by torch.distributed.run)
 
 A step = one data-parallel training iteration of the KGDet detector (configs/kgdet_moment_r50_fpn_1x)
 on a seeded synthetic DeepFashion2-shaped batch of 2 images per GPU at 800x1333 (padded 800x1344):
 forward, the nine losses, backward, gradient all-reduce over RCCL (overlapped with backward),
 grad-clip, Adam step.  Prints ONE JSON line on rank 0.  `value` = images/s over all ranks.
 
-Timing protocol (mmdetection/tools/benchmark.py:84-108 skips its first iterations the same way): after --warmup steps the
+A plain run (no --full) does only what the headline needs: set up, --warmup steps, ONE timed window of exactly --steps
+steps (bracketed by barrier + synchronize, MAX over ranks), the outputs if --dump-outputs is given, the line.
+`ms_per_step` = that window / --steps; `value` = images of the window / its time.
+
+--dump-outputs DIR: what the timed path computed in its LAST timed step, as DIR/<name>.npy (float32), written after the
+timing.  Training: `loss` and every loss term (`loss_<name>`), and a fixed sample (numpy default_rng(0), sorted, <= 4 Mi
+indices into the concatenation of the trainable parameters in model.parameters() order) of the parameters after the
+step's update (`params_sample`) and of their gradients (`grads_sample`).  Inference: per image, the detections of every
+class (`dets_img<i>`: x1, y1, x2, y2, score, class) and their key points (`kpts_img<i>`).  The inputs (weights, batch)
+are seeded: the same arguments give the same inputs in every run.
+
+--full adds everything else the bench measures, as the protocol below describes.
+
+Timing protocol of --full (mmdetection/tools/benchmark.py:84-108 skips its first iterations the same way): after --warmup steps the
 first window of --steps steps is kept as `burst_img_s` (the cold board), then the loop PRE-HEATS by wall time -- windows of
 --steps steps for >= --preheat-s seconds and until three consecutive windows agree within --steady-tol -- because the step
 runs at the board's power limit and the clock settles over the first seconds of load.  `value` is the MEDIAN of the
 --windows (7) timed windows AFTER that (every window bracketed by barrier + synchronize, MAX over ranks); all windows,
 `steady` (do they agree within 3 %), and the board's power / clock read from sysfs or a rocm-smi child are on the line.
 
-Extra objects on the same line:
+Extra objects on the same line (--full):
   roofline     -- the dominant hand-written launch (DeformConv forward of one head stage: 2 maps x 3x3/5x5/7x7, B=2:
                   45.69 GFLOP, 72.1 MB algorithmic) timed live with HIP events on the stream it runs on;
   cpu_baseline -- the oracle's reference-algorithm deformable conv (materialised im2col + GEMM) forward AND backward of
@@ -55,14 +68,14 @@ def parse_args():
                     help='training mode, 1 GPU: skip the bf16 batch-8 inference measurement (a child process) that '
                          'is reported as the `inference` object of the same JSON line')
     ap.add_argument('--windows', type=int, default=7,
-                    help='timed windows of --steps steps each (every window bracketed by barrier + synchronize); `value` is '
+                    help='--full: timed windows of --steps steps each (every window bracketed by barrier + synchronize); `value` is '
                          'the MEDIAN window, min / max / all windows are reported beside it')
     ap.add_argument('--force-dist', action='store_true',
                     help='run the N-rank code path even with --gpus 1: ranks started through a child torch.distributed.run, '
                          'init_process_group(nccl), broadcast, overlapped bucketed all-reduce over RCCL, barriers, '
                          'MAX-reduced time and the `allreduce` object (what a 1-GPU box can prove of the multi-GPU path)')
     ap.add_argument('--preheat-s', type=float, default=8.0,
-                    help='training: untimed pre-heat AFTER --warmup, in windows of --steps steps, for at least this many '
+                    help='--full, training: untimed pre-heat AFTER --warmup, in windows of --steps steps, for at least this many '
                          'seconds of steps AND until three consecutive windows agree within --steady-tol (the board clocks '
                          'down to its power limit over the first seconds of load; `value` is the rate after that ramp)')
     ap.add_argument('--preheat-max-s', type=float, default=30.0, help='give up waiting for a steady state after this long')
@@ -70,7 +83,7 @@ def parse_args():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--mixed-shapes', action='store_true',
                     help='every second image of the batch has a smaller pad_shape of its own (invalid grid points); without the flag '
-                         'the training bench times ONE extra window on such a batch and reports it as `mixed_shapes`')
+                         'the training bench with --full times three extra windows on such a batch and reports them as `mixed_shapes`')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--pipeline', type=int, choices=[0, 1], default=1,
                     help='inference with --graph 1: overlap the result copy + host unpacking of batch k with batch k + 1 '
@@ -81,6 +94,13 @@ def parse_args():
     ap.add_argument('--graphed-step-child', action='store_true', help=argparse.SUPPRESS)
     ap.add_argument('--no-exact-leg', action='store_true',
                     help='training: skip the short window in plain fp32 arithmetic (`exact_fp32` on the line)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the pre-heat and the median of --windows windows, the mixed-shapes '
+                         'window, rooflines and backward products, the exact-fp32 window, the graphed-step and inference '
+                         'children, the CPU baseline, board readings, the N-rank exchange figures.  Without it: --warmup '
+                         'steps, then ONE timed window of --steps steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last timed step to DIR/<name>.npy (see the module docstring)')
     return ap.parse_args()
 
 
@@ -713,7 +733,7 @@ def inference_leg():
     environment variable that must be set before MIOpen initialises; the child is started, never exec'ed)."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--mode', 'infer', '--dtype', 'bf16', '--imgs-per-gpu', '8',
-           '--steps', '30', '--warmup', '5', '--no-cpu-baseline']
+           '--steps', '30', '--warmup', '5', '--no-cpu-baseline', '--full']
     env = {k: v for k, v in os.environ.items() if k != 'MIOPEN_USER_DB_PATH'}
     try:
         res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -739,6 +759,39 @@ def graphed_step_leg(args):
         return json.loads(line)
     except Exception as e:
         return {'error': '%s: %s' % (type(e).__name__, e)}
+
+
+DUMP_SAMPLE = 1 << 22       # sampled elements of the parameters and of the gradients: 16 MB each in float32
+
+
+def dump_outputs(out_dir, mode, last, params=None):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last timed step, as float32 .npy files"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    if mode == 'train':
+        save('loss', last['loss'].detach().float().cpu().numpy())
+        for k, v in last['losses'].items():
+            if 'loss' in k:
+                vs = v if isinstance(v, (list, tuple)) else [v]
+                save(k if k.startswith('loss') else 'loss_' + k,
+                     np.stack([x.detach().float().reshape(-1).cpu().numpy() for x in vs]))
+        with torch.no_grad():
+            flat = torch.cat([p.detach().float().reshape(-1) for p in params])
+            grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                               for p in params])
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+        idx = torch.from_numpy(idx).to(flat.device)
+        save('params_sample', flat.index_select(0, idx).cpu().numpy())
+        save('grads_sample', grads.index_select(0, idx).cpu().numpy())
+    else:
+        for i, r in enumerate(last['res']):
+            boxes = [np.concatenate([d, np.full((len(d), 1), c, np.float32)], 1) for c, d in enumerate(r[0])]
+            save('dets_img%d' % i, np.concatenate(boxes, 0) if boxes else np.zeros((0, 6), np.float32))
+            kpts = [k.reshape(len(k), -1) for k in r[2]] if len(r) > 2 else []
+            save('kpts_img%d' % i, np.concatenate(kpts, 0) if kpts else np.zeros((0, 0), np.float32))
 
 
 def main():
@@ -778,6 +831,7 @@ def main():
             dist.broadcast(p.data, 0)
     batch = synthetic.make_batch(args.imgs_per_gpu, device, seed=rank, mixed_shapes=args.mixed_shapes)
     autocast = torch.autocast('cuda', dtype=torch.bfloat16, enabled=args.dtype == 'bf16')
+    last = {}       # what the latest step returned (--dump-outputs)
 
     if args.mode == 'train':
         model.train()
@@ -795,6 +849,7 @@ def main():
             loss = sum(v.float() if torch.is_tensor(v) else sum(x.float() for x in v) for k, v in losses.items()
                        if 'loss' in k)
             hook.step(model, optimizer, loss)
+            last['losses'], last['loss'] = losses, loss
             return loss
 
         if args.graphed_step_child:
@@ -859,6 +914,7 @@ def main():
                 with torch.no_grad(), autocast:
                     res = model.simple_test_batch(batch['img'], batch['img_meta'], rescale=True)
             n_det[0] = sum(sum(len(d) for d in r[0]) for r in res)
+            last['res'] = res
             return res
 
         def flush():
@@ -866,6 +922,7 @@ def main():
                 res = run.collect(pending[0])
                 pending[0] = None
                 n_det[0] = sum(sum(len(d) for d in r[0]) for r in res)
+                last['res'] = res
 
     # Inference runs as a serving loop would: ONE autocast scope around all batches, so autocast's weight cache keeps
     # the bf16 copies of the FPN / head convolution weights instead of re-casting them every batch (44 launches).
@@ -892,7 +949,7 @@ def main():
             dt = float(t.item())
         return dt
 
-    board = BoardSampler(local_rank) if rank == 0 else None
+    board = BoardSampler(local_rank) if rank == 0 and args.full else None
     preheat = {'windows_img_s': [], 'seconds': 0.0}
     burst = None
     with scope:
@@ -904,7 +961,7 @@ def main():
         import gc
         gc.collect()
         gc.freeze()
-        if args.mode == 'train' and args.preheat_s > 0:
+        if args.full and args.mode == 'train' and args.preheat_s > 0:
             # Pre-heat by wall time.  Every decision below is taken on MAX-reduced window times, i.e. on numbers that are
             # identical on all ranks, so all ranks run the same number of steps (the step contains collectives).
             burst = timed_window()                      # the cold board: what round 3 reported as the headline
@@ -920,11 +977,13 @@ def main():
                        'seconds': round(spent, 2)}
         if board is not None:
             board.start()
-        windows = [timed_window() for _ in range(max(1, args.windows))]
+        windows = [timed_window() for _ in range(max(1, args.windows) if args.full else 1)]
         if board is not None:
             board.stop()
+        if args.dump_outputs and rank == 0:      # (the timed window has collected the last inference batch already)
+            dump_outputs(args.dump_outputs, args.mode, last, params if args.mode == 'train' else None)
         mixed_window = None
-        if args.mode == 'train' and not args.mixed_shapes and not dist_on:
+        if args.full and args.mode == 'train' and not args.mixed_shapes and not dist_on:
             # the step real DeepFashion2 batches take (imgs_per_gpu = 2 mixes aspect ratios): one window on a mixed-shape batch
             keep = batch
             batch = synthetic.make_batch(args.imgs_per_gpu, device, seed=rank, mixed_shapes=True)
@@ -933,7 +992,7 @@ def main():
             mixed_window = sorted(timed_window() for _ in range(3))[1]      # (median of three: one window caught a 28 % hiccup once)
             batch = keep
         exposed, reducer_stats = None, None
-        if dist_on and args.mode == 'train':
+        if args.full and dist_on and args.mode == 'train':
             red = hook._reducer
             if red is not None and red.buckets:
                 before = red.launched_from_hooks
@@ -963,7 +1022,7 @@ def main():
                 bucket_times = red.bucket_trace()
     dt = sorted(windows)[len(windows) // 2]
 
-    ar = allreduce_busbw(device, world) if (dist_on and args.mode == 'train') else None
+    ar = allreduce_busbw(device, world) if (args.full and dist_on and args.mode == 'train') else None
     if ar is not None:
         ar['exposed_ms'] = round(exposed * 1e3, 3)
         ar['exposed_spread_ms'] = round(exposed_spread * 1e3, 3)
@@ -985,14 +1044,15 @@ def main():
             'windows': {'n': len(windows), 'steps_each': args.steps, 'statistic': 'median',
                         'img_s': [round(imgs / w, 1) for w in windows],
                         'min': round(imgs / max(windows), 1), 'max': round(imgs / min(windows), 1)},
-            # steady: the windows agree within 3 % -- judged on the windows WITHOUT the slowest and the fastest one when
-            # there are at least five (this loop is paced by the host within a few percent of the GPU time, and the GPU box's
-            # host is shared: a neighbour's burst reads as one 0.25 s window at -10 %; all windows are listed above)
-            'steady': bool((lambda w: max(w) / min(w) - 1.0 < 0.03)(sorted(windows)[1:-1] if len(windows) >= 5 else windows)),
-            'steady_rule': 'max / min - 1 < 3 % over the windows without the slowest and the fastest',
-            'burst_img_s': round(imgs / burst, 1) if burst else None,
-            'preheat': preheat,
-            'board': board.summary() if board is not None else None,
+            **({
+                # steady: the windows agree within 3 % -- judged on the windows WITHOUT the slowest and the fastest one when
+                # there are at least five (this loop is paced by the host within a few percent of the GPU time, and the GPU
+                # box's host is shared: a neighbour's burst reads as one 0.25 s window at -10 %; all windows are listed above)
+                'steady': bool((lambda w: max(w) / min(w) - 1.0 < 0.03)(sorted(windows)[1:-1] if len(windows) >= 5 else windows)),
+                'steady_rule': 'max / min - 1 < 3 % over the windows without the slowest and the fastest',
+                'burst_img_s': round(imgs / burst, 1) if burst else None,
+                'preheat': preheat,
+                'board': board.summary() if board is not None else None} if args.full else {}),
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32 (3 MFMA products per multiply on hi/lo-split operands -- fp16 parts forward, bf16 parts for gradients --, f32 accumulate)' if args.dtype == 'fp32'
             else 'bf16 (dense convs and deformable operands, f32 accumulate)',
             'data': 'synthetic',
@@ -1008,7 +1068,7 @@ def main():
                                            'backbone + FPN + DeformConv head forward + keypoint-guided decode + NMS'),
                        'global_batch': args.imgs_per_gpu * world, 'parallelism': 'dp%d' % world},
         }
-        if args.mode == 'infer' and use_graph:
+        if args.full and args.mode == 'infer' and use_graph:
             # the same batch with the host->device copy of the fp32 batch INSIDE the step (mmdetection's loader hands over host
             # tensors): (a) copy, then compute, on one stream; (b) the serving arrangement -- batch k + 1 copied on a side stream
             # into a second device buffer while batch k computes, a device-to-device copy into the graph's input at step start
@@ -1089,7 +1149,7 @@ def main():
                                       'copied to page-locked host memory and unpacked per image and class inside the timed window'
                                       if use_graph else 'fp32 batch resident in HBM')
             out['config']['pipelined'] = bool(pipelined)
-        if args.mode == 'train':
+        if args.full and args.mode == 'train':
             # the whole step against the split-operand MFMA roof: algorithmic flops of one step (tools/step_flops.py: dense + deformable
             # convolutions, forward + the gradients a step computes; frozen stem / layer 1 forward only) over the measured step time
             # (kgdet_step_flops above)
@@ -1109,12 +1169,12 @@ def main():
                                    'note': 'three more timed windows (median) of the same step on a batch whose second image has a smaller '
                                            'pad_shape of its own (synthetic.mixed_shapes_of): invalid grid points, same sync-free path '
                                            '(valid extents in the dense targets / fused loss kernels; tests/test_gpu_head.py)'}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             if args.mode == 'train':
                 out['roofline'] = dcn_roofline(device, 2, 'split')
             else:      # the grouped forward the inference batch actually runs
                 out['roofline'] = dcn_roofline(device, args.imgs_per_gpu, 'bf16' if args.dtype == 'bf16' else 'split')
-        if not args.no_roofline and args.mode == 'train' and args.config == 'kgdet':
+        if args.full and not args.no_roofline and args.mode == 'train' and args.config == 'kgdet':
             bw = dcn_backward_products_live(device)
             bw_t = dcn_backward_products_live(device, regime='trained')
             bw_s = dcn_backward_products_live(device, regime='step') if os.path.isfile(os.path.join(ROOT, STEP_OFFSETS)) else {}
@@ -1137,7 +1197,7 @@ def main():
             rl['launch_us_note'] = ('launch_us / frac: dcn_build_taps + dcn_fwd_plane<2> + dcn_fwd_fixup_static with the weight images '
                                     'packed beforehand (an unchanged weight is packed once); *_pack_inside: the same plus '
                                     'dcn_pack_weight_all_multi per call, as in a training step')
-        if args.mode == 'train' and args.config == 'kgdet' and not args.no_exact_leg and world == 1 and not dist_on:
+        if args.full and args.mode == 'train' and args.config == 'kgdet' and not args.no_exact_leg and world == 1 and not dist_on:
             # (one rank only: this block runs on rank 0 alone, a step of an N-rank job contains collectives)
             # the reference's precision class, measured: the same step in plain fp32 arithmetic (f32-input MFMA deformable kernels,
             # MIOpen fp32 convolutions with its heuristic picks -- no find), a short window after the steady ones
@@ -1164,18 +1224,18 @@ def main():
                                      'speedup_of_value': round((imgs / dt) / (args.imgs_per_gpu * world / tex), 3)}
             except Exception as e:
                 out['exact_fp32'] = {'error': '%s: %s' % (type(e).__name__, e)}
-        if args.mode == 'train' and world == 1 and not dist_on and args.dtype == 'fp32' and args.graph_train:
+        if args.full and args.mode == 'train' and world == 1 and not dist_on and args.dtype == 'fp32' and args.graph_train:
             gs = graphed_step_leg(args)
             out['graphed_step'] = gs
             out['eager_step'] = {'img_s': out['value'], 'ms_per_step': out['ms_per_step']}
             # `value` is ALWAYS the median of the timed eager windows above (the ones the driver's clock brackets); the replayed
             # graph -- the same kernels in the same order, measured in a child process -- is reported beside it
             out['step_mode'] = 'eager'
-        if (args.mode == 'train' and world == 1 and args.config == 'kgdet' and not args.no_inference_leg):
+        if (args.full and args.mode == 'train' and world == 1 and args.config == 'kgdet' and not args.no_inference_leg):
             out['inference'] = inference_leg()
         if ar is not None:
             out['allreduce'] = ar
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             rl = out.get('roofline')
             out['cpu_baseline'] = cpu_baseline(device, rl['launch_us'] * 1e-6 if rl and rl.get('launch_us') and
                                                args.mode == 'train' else None)

@@ -1,7 +1,8 @@
 """Generate tests/golden/eval_golden.npz with the REFERENCE evaluator (run in the build container only -- needs
 /root/reference):
 
-    python tests/golden/make_eval_golden.py
+    python tests/golden/make_eval_golden.py         (eval_golden.npz)
+    python tests/golden/make_eval_golden.py live    (eval_live_golden.npz)
 
 Ground truth = the reference's demo annotations (data/demo_dataset/demo_dataset-32.json, copied next to this file as a
 data fixture).  Detections = seeded perturbations of the ground truth (jittered duplicates, wrong categories, pure
@@ -110,5 +111,26 @@ def main():
     np.savez_compressed(os.path.join(HERE, 'eval_golden.npz'), **out)
 
 
+LIVE_SEED = 123
+
+
+def live():
+    """tests/golden/eval_live_golden.npz: the reference evaluator's stats / precision / recall on the detections of
+    tests/test_evaluation.py::test_live_reference_evaluator_agrees_when_present (seed 123), for 'bbox' and 'keypoints'."""
+    ref = build_ref.load_reference_evaluator()
+    assert ref is not None, 'reference checkout not present'
+    gt = json.load(open(GT_FIX))
+    b, k = as_results(*synth_detections(gt, seed=LIVE_SEED))
+    out = {}
+    for typ, res in (('bbox', b), ('keypoints', k)):
+        stats, prec, rec = run_reference(ref[0], ref[1], GT_FIX, res, typ)
+        out['%s_stats' % typ], out['%s_precision' % typ], out['%s_recall' % typ] = stats, prec, rec
+        print('live', typ, np.round(stats, 4))
+    np.savez_compressed(os.path.join(HERE, 'eval_live_golden.npz'), **out)
+
+
 if __name__ == '__main__':
-    main()
+    if 'live' in sys.argv[1:]:
+        live()
+    else:
+        main()

@@ -1,7 +1,9 @@
 """Generate tests/golden/nms_golden.npz with the COMPILED REFERENCE kernels (run in the build
 container only -- needs /root/reference):
 
-    python tests/golden/make_nms_golden.py
+    python tests/golden/make_nms_golden.py          (nms_golden.npz)
+    python tests/golden/make_nms_golden.py large    (nms_large_golden.npz)
+    python tests/golden/make_nms_golden.py live     (nms_live_golden.npz)
 
 Inputs are seeded synthetic boxes; expected outputs are whatever the unmodified reference
 sources (nms_cpu.cpp, soft_nms_cpu.pyx, built by oracle/build_ref.py) return.  The .npz holds
@@ -123,8 +125,44 @@ def large():
     print('wrote', path, os.path.getsize(path), 'bytes')
 
 
+def live_boxes(rng, n):
+    """the inputs of tests/test_oracle_nms.py::test_live_against_compiled_reference (uniform boxes, distinct scores)"""
+    x1 = rng.uniform(0, 500, n); y1 = rng.uniform(0, 500, n)
+    return np.stack([x1, y1, x1 + rng.uniform(1, 300, n), y1 + rng.uniform(1, 300, n),
+                     rng.permutation(n) / n + 0.01], 1).astype(np.float32)
+
+
+LIVE_SIZES = (5, 33, 257, 777)
+LIVE_THRS = (0.3, 0.5, 0.8)
+LIVE_METHODS = ((1, 'linear'), (2, 'gaussian'))
+
+
+def live():
+    """tests/golden/nms_live_golden.npz: what the compiled reference returns for the live test's inputs (seed 7), so the
+    test holds the oracle to the reference where the reference is not mounted.  The boxes are re-created from the seed;
+    their float64 sums are stored as checksums."""
+    import torch
+    ref_nms, ref_soft = build_ref.load()
+    rng = np.random.default_rng(7)
+    out = {}
+    for n in LIVE_SIZES:
+        d = live_boxes(rng, n)
+        out['checksum_n%d' % n] = np.float64(d.astype(np.float64).sum())
+        for thr in LIVE_THRS:
+            out['keep_n%d_t%g' % (n, thr)] = ref_nms.nms(torch.from_numpy(d), thr).numpy().astype(np.int64)
+            for m, name in LIVE_METHODS:
+                rd, ri = ref_soft(d, thr, method=m, sigma=0.5, min_score=0.05)
+                out['soft_%s_n%d_t%g_dets' % (name, n, thr)] = np.asarray(rd, np.float32)
+                out['soft_%s_n%d_t%g_inds' % (name, n, thr)] = np.asarray(ri, np.int64)
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'nms_live_golden.npz')
+    np.savez_compressed(path, **out)
+    print('wrote', path, os.path.getsize(path), 'bytes')
+
+
 if __name__ == '__main__':
     if 'large' in sys.argv[1:]:
         large()
+    elif 'live' in sys.argv[1:]:
+        live()
     else:
         main()

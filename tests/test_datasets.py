@@ -151,10 +151,10 @@ def test_collate_pads_to_the_largest_image():
 
 
 def test_real_demo_images_decode_when_reference_is_present():
-    root = '/root/reference/data/demo_dataset/image/'
-    if not os.path.isdir(root):
-        pytest.skip('reference checkout not present')
+    # the demo set's first image (data fixture: tests/golden/demo_images/, copied from the reference's demo_dataset/image/)
+    root = os.path.join(HERE, 'golden', 'demo_images')
     d = _dataset(img_prefix=root)
+    assert os.path.isfile(os.path.join(root, d.img_infos[0]['filename']))
     s = d[0]
     info = d.img_infos[0]
     assert s['img_meta']['ori_shape'] == (info['height'], info['width'], 3)

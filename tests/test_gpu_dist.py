@@ -267,7 +267,8 @@ def test_bench_force_dist_runs_the_n_rank_path_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MIOPEN_USER_DB_PATH')}
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--force-dist', '--steps', '4',
-                          '--warmup', '3', '--windows', '2', '--no-cpu-baseline', '--no-roofline', '--no-inference-leg'],
+                          '--warmup', '3', '--windows', '2', '--no-cpu-baseline', '--no-roofline', '--no-inference-leg',
+                          '--full'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     line = [l for l in res.stdout.decode().splitlines() if l.startswith('{')][-1]
@@ -293,7 +294,7 @@ def test_bench_two_rank_rehearsal_completes(mode):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MIOPEN_USER_DB_PATH')}
     env['KGDET_BENCH_REHEARSAL'] = '1'
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--windows', '2',
-           '--preheat-s', '0', '--no-roofline', '--no-cpu-baseline']
+           '--preheat-s', '0', '--no-roofline', '--no-cpu-baseline', '--full']
     if mode == 'infer':
         cmd += ['--mode', 'infer', '--dtype', 'bf16', '--imgs-per-gpu', '2']
     res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -319,7 +320,7 @@ def test_bench_two_ranks_over_rccl_when_the_box_has_two_gpus():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MIOPEN_USER_DB_PATH',
                                                             'KGDET_BENCH_REHEARSAL')}
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '3',
-                          '--windows', '2', '--preheat-s', '0', '--no-roofline', '--no-cpu-baseline'],
+                          '--windows', '2', '--preheat-s', '0', '--no-roofline', '--no-cpu-baseline', '--full'],
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     d = json.loads([l for l in res.stdout.decode().splitlines() if l.startswith('{')][-1])

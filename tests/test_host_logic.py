@@ -13,6 +13,23 @@ from kgdet_amd.registry import (HEADS, Config, ConfigDict, Registry, build_detec
 from tests import cpu_ops
 
 REF_CFG = '/root/reference/configs/kgdet_moment_r50_fpn_1x-demo.py'
+REF_CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_configs_golden.txt')
+
+
+def _reference_config(name):
+    """The reference's configs/<name>.py as Config.fromfile evaluates it.  Its model / train_cfg / test_cfg are recorded in
+    tests/golden/ref_configs_golden.txt (tests/golden/make_config_golden.py); where the reference checkout is mounted the
+    file itself is loaded and must equal the record."""
+    import ast
+    with open(REF_CONFIGS) as f:
+        rec = Config(ast.literal_eval(f.read())[name])
+    path = os.path.join(os.path.dirname(REF_CFG), name + '.py')
+    if not os.path.isfile(path):
+        return rec
+    cfg = Config.fromfile(path)
+    for k in ('model', 'train_cfg', 'test_cfg'):
+        assert cfg[k] == rec[k], (name, k)
+    return cfg
 
 
 # ---- registry / config --------------------------------------------------------------------------
@@ -61,22 +78,20 @@ def test_config_dict_access(tmp_path):
         Config.fromfile(str(tmp_path / 'c.yaml'))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason='reference configs not mounted')
 def test_reference_configs_load_unchanged():
-    cfg = Config.fromfile(REF_CFG)
+    cfg = _reference_config('kgdet_moment_r50_fpn_1x-demo')
     mine = configs.kgdet_r50_fpn()
     assert cfg.model == mine.model and cfg.train_cfg == mine.train_cfg and cfg.test_cfg == mine.test_cfg
     model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
     n = sum(p.numel() for p in model.parameters() if p.requires_grad)
     assert n == 59134423
-    full = Config.fromfile(REF_CFG.replace('-demo', '-deepfashion2'))
+    full = _reference_config('kgdet_moment_r50_fpn_1x-deepfashion2')
     assert full.model == mine.model
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CFG), reason='reference configs not mounted')
 @pytest.mark.parametrize('name,parallel', [('serial', False), ('parallel', True)])
 def test_reference_serial_parallel_configs_load_unchanged(name, parallel):
-    cfg = Config.fromfile('/root/reference/configs/reppoints_moment_%s_r50_fpn_1x-deepfashion2.py' % name)
+    cfg = _reference_config('reppoints_moment_%s_r50_fpn_1x-deepfashion2' % name)
     mine = configs.reppoints_kp_r50_fpn(parallel=parallel)
     assert cfg.model == mine.model and cfg.train_cfg == mine.train_cfg and cfg.test_cfg == mine.test_cfg
     head = build_head(cfg.model.bbox_head)

@@ -67,24 +67,33 @@ def test_soft_nms_bad_method():
         oracle.soft_nms(np.zeros((1, 5), np.float32), 0.5, method='nope')
 
 
-@pytest.mark.skipif(not build_ref.available(), reason='reference sources not mounted')
-def test_live_against_compiled_reference():
-    """Fresh random inputs through the compiled reference ($KGDET_REF_BUILD, outside the tree) and the restatement."""
-    import torch
-    ref_nms, ref_soft = build_ref.load()
+def test_live_against_compiled_reference(golden_dir):
+    """Seeded random inputs through the restatement against the compiled reference's outputs for them
+    (tests/golden/nms_live_golden.npz, `make_nms_golden.py live`); where the reference sources are mounted, the compiled
+    reference ($KGDET_REF_BUILD, outside the tree) is also run live on the same inputs."""
+    from tests.golden.make_nms_golden import LIVE_METHODS, LIVE_SIZES, LIVE_THRS, live_boxes
+    R = np.load(os.path.join(golden_dir, 'nms_live_golden.npz'))
+    ref = None
+    if build_ref.available():
+        import torch
+        ref = build_ref.load()
     rng = np.random.default_rng(7)
-    for n in (5, 33, 257, 777):
-        x1 = rng.uniform(0, 500, n); y1 = rng.uniform(0, 500, n)
-        d = np.stack([x1, y1, x1 + rng.uniform(1, 300, n), y1 + rng.uniform(1, 300, n),
-                      rng.permutation(n) / n + 0.01], 1).astype(np.float32)
-        for thr in (0.3, 0.5, 0.8):
-            np.testing.assert_array_equal(oracle.nms(d, thr),
-                                          ref_nms.nms(torch.from_numpy(d), thr).numpy())
-            for m, name in ((1, 'linear'), (2, 'gaussian')):
-                rd, ri = ref_soft(d, thr, method=m, sigma=0.5, min_score=0.05)
+    for n in LIVE_SIZES:
+        d = live_boxes(rng, n)
+        assert float(d.astype(np.float64).sum()) == float(R['checksum_n%d' % n])     # the same boxes as the generator's
+        for thr in LIVE_THRS:
+            keep = oracle.nms(d, thr)
+            np.testing.assert_array_equal(keep, R['keep_n%d_t%g' % (n, thr)])
+            if ref is not None:
+                np.testing.assert_array_equal(keep, ref[0].nms(torch.from_numpy(d), thr).numpy())
+            for m, name in LIVE_METHODS:
                 od, oi = oracle.soft_nms(d, thr, name, 0.5, 0.05)
-                np.testing.assert_array_equal(oi, ri)
-                np.testing.assert_array_equal(od, np.asarray(rd, np.float32))
+                np.testing.assert_array_equal(oi, R['soft_%s_n%d_t%g_inds' % (name, n, thr)])
+                np.testing.assert_array_equal(od, R['soft_%s_n%d_t%g_dets' % (name, n, thr)])
+                if ref is not None:
+                    rd, ri = ref[1](d, thr, method=m, sigma=0.5, min_score=0.05)
+                    np.testing.assert_array_equal(oi, ri)
+                    np.testing.assert_array_equal(od, np.asarray(rd, np.float32))
 
 
 def test_nms_large_segments_match_reference_golden(golden_dir):

@@ -1,9 +1,10 @@
 #!/bin/bash
 # per-launch durations of one kernel (name substring $1) over the last steady step of the config-5 training bench; run through gpurun
+ROOT=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=/tmp/kl
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --config ${2:-serial} --steps 3 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline --no-inference-leg > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$ROOT"/bench.py --full --config ${2:-serial} --steps 3 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline --no-inference-leg > $OUT/log 2>&1
 python3 - "$1" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open('/tmp/kl/t_kernel_trace.csv')))

@@ -1,9 +1,10 @@
 #!/bin/bash
 # min / median / max duration per kernel over the last steady step of the training bench (config $1: kgdet | serial); run through gpurun
+ROOT=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=/tmp/ks
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --config ${1:-kgdet} --steps 3 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline --no-inference-leg > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$ROOT"/bench.py --full --config ${1:-kgdet} --steps 3 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline --no-inference-leg > $OUT/log 2>&1
 python3 - <<'PY'
 import csv, collections
 rows = list(csv.DictReader(open('/tmp/ks/t_kernel_trace.csv')))

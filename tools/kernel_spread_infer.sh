@@ -1,9 +1,10 @@
 #!/bin/bash
 # min / median / max duration per kernel over the last batch of the bf16 batch-8 inference bench; run through gpurun
+ROOT=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=/tmp/ksi
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --mode infer --dtype bf16 --imgs-per-gpu 8 --steps 6 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$ROOT"/bench.py --full --mode infer --dtype bf16 --imgs-per-gpu 8 --steps 6 --warmup 2 --windows 1 --no-cpu-baseline --no-roofline > $OUT/log 2>&1
 python3 - <<'PY'
 import csv, collections
 rows = list(csv.DictReader(open('/tmp/ksi/t_kernel_trace.csv')))

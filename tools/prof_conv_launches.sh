@@ -1,9 +1,10 @@
 #!/bin/bash
 # per-launch workgroup counts and durations of the dense convolution kernels in one steady training step (run on the GPU box)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=/tmp/convl
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-roofline > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$ROOT"/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-roofline > $OUT/log 2>&1
 python3 - <<'PY'
 import csv, collections
 rows = list(csv.DictReader(open('/tmp/convl/t_kernel_trace.csv')))

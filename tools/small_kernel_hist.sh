@@ -1,8 +1,9 @@
 #!/bin/bash
 # per-launch durations of the bookkeeping kernels of one training step (rocprofv3 kernel trace); run through gpurun
+ROOT=$(cd "$(dirname "$0")/.." && pwd)    # the repository
 OUT=/tmp/skh; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 2 --windows 1 --no-inference-leg --no-cpu-baseline --no-roofline > $OUT/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT -o t -- python3 "$ROOT"/bench.py --full --steps 3 --warmup 2 --windows 1 --no-inference-leg --no-cpu-baseline --no-roofline > $OUT/log 2>&1
 python3 - <<'PY'
 import csv, collections
 rows = list(csv.DictReader(open('/tmp/skh/t_kernel_trace.csv')))
