@@ -572,10 +572,15 @@ size_t kgdet_nms_workspace_bytes(int64_t total_n, int32_t num_segments);
  * nothing read by the host: per (image, class) the candidates with score > score_thr are suppressed as kgdet_nms does;
  * per image the classes' survivors are concatenated (class order, ascending candidate row) and, beyond max_num, the
  * max_num highest scores are kept (ties: earlier first).  boxes [B, N, 4]; scores [B, N, score_stride] with class c in
- * column score_col0 + c (C <= 64, N <= 4096, N*C <= 16384); out_det [B, max_num, 5]; out_label (0-based class) and
- * out_src (candidate row, for gathering the landmarks) [B, max_num] int64; out_count [B] int64; rows past the count
- * are zero.  workspace: kgdet_multiclass_nms_workspace_bytes(B, N, C). */
+ * column score_col0 + c; out_det [B, max_num, 5]; out_label (0-based class) and out_src (candidate row, for gathering the
+ * landmarks) [B, max_num] int64; out_count [B] int64; rows past the count are zero.  Limits: N <= 4096 (one class's
+ * boxes in LDS), C <= 64, C * min(N, max_num) <= 16384 (the select keys at most the first max_num survivors of a class by
+ * score; a flip-TTA set of 2 x 1000 candidates x 13 classes with max_num 100 fits).
+ * workspace: kgdet_multiclass_nms_workspace_bytes(B, N, C). */
 size_t kgdet_multiclass_nms_workspace_bytes(int32_t B, int32_t N, int32_t C);
+/* 1 when kgdet_multiclass_nms serves this problem (the limits above), 0 when it returns KGDET_E_UNSUPPORTED: the one
+ * statement of the limits (callers deciding before a graph capture). */
+int kgdet_multiclass_nms_supported(int32_t B, int32_t N, int32_t C, int32_t max_num);
 int kgdet_multiclass_nms(const float *boxes, const float *scores, int32_t B, int32_t N, int32_t C,
                          int32_t score_stride, int32_t score_col0, float score_thr, float iou_thr, int32_t max_num,
                          float *out_det, int64_t *out_label, int64_t *out_src, int64_t *out_count, void *workspace,
@@ -598,6 +603,24 @@ int kgdet_multiclass_soft_nms(const float *boxes, const float *scores, int32_t B
                               int32_t method, float sigma, float min_score, int32_t max_num, float *out_det,
                               int64_t *out_label, int64_t *out_src, int64_t *out_count, void *workspace,
                               size_t workspace_bytes, void *stream);
+/* Test-time augmentation merge (RepPointsDetectorKp.aug_test): A <= 16 augmentations of one image, each with its decoded
+ * candidates in its own resized frame -- boxes [n, 4], scores [n, score_stride], landmarks [n, K, 3] (x, y, v), all
+ * float32 and contiguous -- are mapped back to the original frame and concatenated in augmentation order into out_boxes
+ * [T, 4], out_scores [T, score_stride], out_kpts [T, K, 3] (T = sum of n).  Per augmentation: when `flip`,
+ * x1' = (img_w - x2) - 1, x2' = (img_w - x1) - 1, landmark x' = (img_w - x) - 1 and out slot k takes input slot
+ * kpt_perm[k] (device int32 [K], an involution: flip_indices[0::2] // 2); then box coordinates and landmark x, y are
+ * multiplied by (float)(1.0 / scale) (torch's division of a GPU tensor by a python float); visibility and scores are
+ * copied.  One launch, the segments passed by value (capturable); n = 0 is allowed; kpt_perm may be NULL when no
+ * segment is flipped.  K <= 1024; A > 16 returns KGDET_E_UNSUPPORTED. */
+typedef struct kgdet_aug_segment {
+  const float *boxes, *scores, *kpts;
+  int64_t n;
+  float img_w;
+  double scale;    /* the python float itself: the reciprocal is rounded to fp32 from double, as torch does */
+  int32_t flip;
+} kgdet_aug_segment;
+int kgdet_aug_merge(const kgdet_aug_segment *segs, int32_t A, int32_t score_stride, int32_t K, const int32_t *kpt_perm,
+                    float *out_boxes, float *out_scores, float *out_kpts, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

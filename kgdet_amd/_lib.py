@@ -36,6 +36,12 @@ class PsroiShape(ctypes.Structure):
         ('spatial_scale', ctypes.c_float), ('trans_std', ctypes.c_float)]
 
 
+class AugSegment(ctypes.Structure):
+    """kgdet_aug_segment (one test-time augmentation's decoded candidates)"""
+    _fields_ = [('boxes', ctypes.c_void_p), ('scores', ctypes.c_void_p), ('kpts', ctypes.c_void_p), ('n', ctypes.c_int64),
+                ('img_w', ctypes.c_float), ('scale', ctypes.c_double), ('flip', ctypes.c_int32)]
+
+
 def build(force=False):
     """Compile every HIP source for gfx950 into kgdet_amd/libkgdet_hip.so (hipcc, in-tree)."""
     cmd = ['make', '-C', CSRC, '-j8']
@@ -64,9 +70,10 @@ def lib():
                      'kgdet_moment_bbox_backward_workspace_bytes', 'kgdet_multiclass_soft_nms_workspace_bytes'):
             if hasattr(L, name):
                 getattr(L, name).restype = ctypes.c_size_t
-        if hasattr(L, 'kgdet_multiclass_soft_nms_supported'):
-            L.kgdet_multiclass_soft_nms_supported.restype = ctypes.c_int
-            L.kgdet_multiclass_soft_nms_supported.argtypes = [ctypes.c_int32] * 4
+        for name in ('kgdet_multiclass_soft_nms_supported', 'kgdet_multiclass_nms_supported'):
+            if hasattr(L, name):
+                getattr(L, name).restype = ctypes.c_int
+                getattr(L, name).argtypes = [ctypes.c_int32] * 4
         _lib = L
     return _lib
 

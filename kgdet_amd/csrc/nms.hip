@@ -72,12 +72,15 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int *lds_wave_sums, i
 // One problem: n boxes at box[i * box_stride + 0..3], scores at score[i * score_stride]; with `filter` only the
 // boxes whose score is > score_thr take part (the per-class candidate filter of multiclass_nms_kp,
 // bbox_nms_kp.py:28-33, done in place instead of by compaction); kept ORIGINAL indices, ascending, go to out[].
+// With `rank` (on-chip only) each out[] entry also carries, in bits 32..63, the survivor's rank in the suppression
+// order (score descending, index ascending): multiclass_select keys only the first max_num of a class by that rank.
 struct NmsProblem {
   const float *box;
   int box_stride;
   const float *score;
   int score_stride;
   bool filter;
+  bool rank;
   float score_thr;
   int n;
   long long *out;
@@ -209,8 +212,19 @@ __device__ __forceinline__ void nms_block(const NmsProblem pr, float thr, const 
     __syncthreads();
     for (int i = tid; i < n_all; i += kNmsThreads) flag[i] = 0;
     __syncthreads();
-    for (int i = tid, m = 0; i < n; i += kNmsThreads, ++m)
-      if (keep_sorted_local[m]) flag[(unsigned)(keys[i] & 0xffffffffu)] = 1;
+    if (pr.rank) {   // flag = 1 + rank among the survivors in sorted order (each thread a contiguous run of it)
+      const int per_s = (n + kNmsThreads - 1) / kNmsThreads;
+      const int s_lo = min(n, tid * per_s), s_hi = min(n, s_lo + per_s);
+      int alive_cnt = 0;
+      for (int i = s_lo; i < s_hi; ++i) alive_cnt += alive[i];
+      int unused;
+      int r = block_exclusive_scan(alive_cnt, wave_sums, unused);
+      for (int i = s_lo; i < s_hi; ++i)
+        if (alive[i]) flag[(unsigned)(keys[i] & 0xffffffffu)] = 1 + r++;
+    } else {
+      for (int i = tid, m = 0; i < n; i += kNmsThreads, ++m)
+        if (keep_sorted_local[m]) flag[(unsigned)(keys[i] & 0xffffffffu)] = 1;
+    }
   } else {
     for (int i = tid; i < n_all; i += kNmsThreads) flag[i] = 0;
     __syncthreads();
@@ -222,11 +236,11 @@ __device__ __forceinline__ void nms_block(const NmsProblem pr, float thr, const 
   const int per = (n_all + kNmsThreads - 1) / kNmsThreads;
   const int lo = tid * per, hi = min(n_all, lo + per);
   int cnt = 0;
-  for (int i = lo; i < hi; ++i) cnt += flag[i];
+  for (int i = lo; i < hi; ++i) cnt += flag[i] != 0;
   int total;
   int pos = block_exclusive_scan(cnt, wave_sums, total);
   for (int i = lo; i < hi; ++i)
-    if (flag[i]) pr.out[pos++] = i;
+    if (flag[i]) pr.out[pos++] = pr.rank ? (((long long)(flag[i] - 1) << 32) | i) : i;
   if (tid == 0) *pr.num_out = total;
 }
 
@@ -279,6 +293,7 @@ __global__ __launch_bounds__(kNmsThreads) void nms_segments_large(const float *_
   pr.score = pr.box + 4;
   pr.score_stride = 5;
   pr.filter = false;
+  pr.rank = false;
   pr.score_thr = 0.f;
   pr.n = (int)n;
   pr.out = keep + seg_begin;
@@ -302,6 +317,7 @@ __global__ __launch_bounds__(kNmsThreads) void nms_segments(const float *__restr
   pr.score = pr.box + 4;
   pr.score_stride = 5;
   pr.filter = false;
+  pr.rank = false;
   pr.score_thr = 0.f;
   pr.n = (int)(seg_offsets[seg + 1] - seg_begin);
   pr.out = keep + seg_begin;
@@ -327,6 +343,7 @@ __global__ __launch_bounds__(kNmsThreads) void multiclass_nms_segments(const flo
   pr.score = scores + (long long)b * N * S + col0 + c;
   pr.score_stride = S;
   pr.filter = true;
+  pr.rank = true;
   pr.score_thr = score_thr;
   pr.n = N;
   pr.out = keep + (long long)seg * N;
@@ -336,7 +353,9 @@ __global__ __launch_bounds__(kNmsThreads) void multiclass_nms_segments(const flo
 
 // The tail of multiclass_nms_kp (bbox_nms_kp.py:52-70) per image: concatenate the classes' survivors (class order,
 // ascending candidate index inside a class); more than max_num -> the max_num best by score (ties: earlier in the
-// concatenation first).  One workgroup per image; keys sorted in LDS.
+// concatenation first).  One workgroup per image; keys sorted in LDS.  Inside a class, (score desc, position asc) is
+// the suppression order of the segment, so an entry of the top max_num is among the first max_num of its class by
+// the rank the segment stored with it: only those (at most C * max_num) are keyed, whatever N is.
 // out_det [B, max_num, 5]; out_label [B, max_num] (0-based class); out_src [B, max_num] (row n of the image's
 // candidate arrays, for gathering landmarks); out_count [B].  Rows past the count are zero.
 __global__ __launch_bounds__(kNmsThreads) void multiclass_select(const float *__restrict__ boxes,
@@ -348,41 +367,43 @@ __global__ __launch_bounds__(kNmsThreads) void multiclass_select(const float *__
                                                                  long long *__restrict__ out_src,
                                                                  long long *__restrict__ out_count, int max_np) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ int prefix[65];
+  __shared__ int prefix[65], tprefix[65];   // full concatenation / truncated (first max_num per class by rank)
   unsigned long long *keys = reinterpret_cast<unsigned long long *>(smem);
   const int b = blockIdx.x, tid = threadIdx.x;
   if (tid == 0) {
-    int run = 0;
+    int run = 0, trun = 0;
     for (int c = 0; c < C; ++c) {
-      prefix[c] = run;
-      run += (int)num_keep[b * C + c];
+      prefix[c] = run; tprefix[c] = trun;
+      const int k = (int)num_keep[b * C + c];
+      run += k; trun += min(k, max_num);
     }
-    prefix[C] = run;
+    prefix[C] = run; tprefix[C] = trun;
   }
   __syncthreads();
-  const int T = prefix[C];
+  const int T = prefix[C], TT = tprefix[C];
   const int out_n = min(T, max_num);
-  auto entry = [&](int p, int &c, int &n) {   // position in the concatenation -> (class, candidate row)
+  // position in the concatenation -> (class, candidate row, rank of the survivor in its class's suppression order)
+  auto entry = [&](int p, int &c, int &n, int &rank) {
     int lo = 0, hi = C - 1;
     while (lo < hi) {
       const int mid = (lo + hi + 1) >> 1;
       if (prefix[mid] <= p) lo = mid; else hi = mid - 1;
     }
     c = lo;
-    n = (int)keep[((long long)b * C + c) * N + (p - prefix[c])];
+    const long long e = keep[((long long)b * C + c) * N + (p - prefix[c])];
+    n = (int)(e & 0xffffffffll);
+    rank = (int)(e >> 32);
   };
   const float *sc = scores + (long long)b * N * S + col0;
   if (T > max_num) {
     int NP = 64;
-    while (NP < T) NP <<= 1;
-    for (int p = tid; p < NP; p += kNmsThreads) {
-      unsigned long long k = ~0ull;
-      if (p < T) {
-        int c, n;
-        entry(p, c, n);
-        k = score_key(sc[(long long)n * S + c], (unsigned)p);
-      }
-      keys[p] = k;
+    while (NP < TT) NP <<= 1;
+    for (int q = tid; q < NP; q += kNmsThreads) keys[q] = ~0ull;
+    __syncthreads();
+    for (int p = tid; p < T; p += kNmsThreads) {
+      int c, n, rank;
+      entry(p, c, n, rank);
+      if (rank < max_num) keys[tprefix[c] + rank] = score_key(sc[(long long)n * S + c], (unsigned)p);
     }
     __syncthreads();
     for (int k = 2; k <= NP; k <<= 1)
@@ -398,12 +419,13 @@ __global__ __launch_bounds__(kNmsThreads) void multiclass_select(const float *__
         __syncthreads();
       }
   }
+  (void)max_np;
   for (int r = tid; r < max_num; r += kNmsThreads) {
     float *od = out_det + ((long long)b * max_num + r) * 5;
     if (r < out_n) {
       const int p = T > max_num ? (int)(keys[r] & 0xffffffffu) : r;
-      int c, n;
-      entry(p, c, n);
+      int c, n, rank;
+      entry(p, c, n, rank);
       const float *bp = boxes + ((long long)b * N + n) * 4;
       od[0] = bp[0]; od[1] = bp[1]; od[2] = bp[2]; od[3] = bp[3];
       od[4] = sc[(long long)n * S + c];
@@ -765,6 +787,14 @@ size_t kgdet_multiclass_nms_workspace_bytes(int32_t B, int32_t N, int32_t C) {
   return ((size_t)B * C * N + (size_t)B * C) * sizeof(int64_t);
 }
 
+// the on-chip limits of kgdet_multiclass_nms in ONE place: a segment's boxes in LDS (N <= 4096), the select's keys (at most
+// min(N, max_num) per class) in 128 KiB of LDS
+int kgdet_multiclass_nms_supported(int32_t B, int32_t N, int32_t C, int32_t max_num) {
+  (void)B;
+  if (N < 0 || N > kNmsMaxLen || C <= 0 || C > 64 || max_num <= 0) return 0;
+  return (long long)C * (N < max_num ? N : max_num) <= 16384 ? 1 : 0;
+}
+
 int kgdet_multiclass_nms(const float *boxes, const float *scores, int32_t B, int32_t N, int32_t C,
                          int32_t score_stride, int32_t score_col0, float score_thr, float iou_thr, int32_t max_num,
                          float *out_det, int64_t *out_label, int64_t *out_src, int64_t *out_count, void *workspace,
@@ -782,16 +812,16 @@ int kgdet_multiclass_nms(const float *boxes, const float *scores, int32_t B, int
   }
   KGDET_CHECK_SHAPE(boxes && scores, "null pointer");
   KGDET_CHECK_SHAPE(workspace && workspace_bytes >= kgdet_multiclass_nms_workspace_bytes(B, N, C), "workspace too small");
-  if (N > kNmsMaxLen || (long long)N * C > 16384) {
-    set_error("multiclass_nms: %d candidates x %d classes exceed the on-chip limits (%d per class, 16384 per image)",
-              N, C, kNmsMaxLen);
+  if (!kgdet_multiclass_nms_supported(B, N, C, max_num)) {
+    set_error("multiclass_nms: %d candidates (limit %d) / %d classes x %d detections (limit 16384 keys) exceed the "
+              "on-chip limits", N, kNmsMaxLen, C, max_num);
     return KGDET_E_UNSUPPORTED;
   }
   int64_t *keep = (int64_t *)workspace, *num_keep = keep + (size_t)B * C * N;
   int np = 64;
   while (np < N) np <<= 1;
-  int np2 = 64;
-  while (np2 < N * C) np2 <<= 1;
+  int np2 = 64;   // multiclass_select keys at most the first min(N, max_num) survivors of each class
+  while (np2 < C * (N < max_num ? N : max_num)) np2 <<= 1;
   static thread_local bool attr_set = false;
   if (!attr_set) {
     KGDET_HIP_TRY(hipFuncSetAttribute((const void *)multiclass_nms_segments,

@@ -4,7 +4,9 @@ Mirrors mmdet/models/detectors/reppoints_detector_kp.py:9-148 on top of
 single_stage.py:9-70 and base.py:12-142 (``forward(img, img_meta, return_loss=True, **kw)``
 dispatch, ``forward_train``, ``simple_test``, ``bbox2result_kp``).  The reference asserts one
 image per GPU at test time (base.py:75-76); ``simple_test_batch`` lifts that for the batch-8
-inference configuration, running decode + NMS for the whole batch at once.
+inference configuration, running decode + NMS for the whole batch at once.  ``aug_test`` is mmdetection's flip /
+multi-scale test-time augmentation with the landmarks carried through (upstream reppoints_detector.py:27-82 semantics;
+the reference's own ``aug_test`` at reppoints_detector_kp.py:118-148 cannot run).
 """
 import numpy as np
 import torch
@@ -187,8 +189,43 @@ class RepPointsDetectorKp(nn.Module):
     def simple_test(self, img, img_meta, rescale=False):
         return self.simple_test_batch(img, img_meta, rescale)[0]
 
+    def aug_candidates(self, imgs, img_metas):
+        """every augmentation's decoded candidates in its own resized frame: a list, in the order of ``imgs``, of
+        (bboxes [n,4], scores [n,1+C], kpts [n,K,3]) from ``get_bboxes(..., rescale=False, nms=False)``.  Augmentations
+        with the same tensor shape (an image and its flip always) share one forward pass."""
+        metas = [m[0] for m in img_metas]
+        groups = {}
+        for i, t in enumerate(imgs):
+            groups.setdefault(tuple(t.shape[1:]), []).append(i)
+        cands = [None] * len(imgs)
+        for idx in groups.values():
+            img = imgs[idx[0]] if len(idx) == 1 else torch.cat([imgs[i] for i in idx])
+            group_metas = [metas[i] for i in idx]
+            outs = self.bbox_head(self.extract_feat(img), group_metas)
+            for i, c in zip(idx, self.bbox_head.get_bboxes(*(outs + (group_metas, self.test_cfg, False, False)))):
+                cands[i] = c
+        return cands
+
+    def merge_aug_detections(self, cands, img_metas, rescale=False):
+        """steps after ``aug_candidates``: map back + merge (``kgdet_aug_merge`` for GPU candidates, the restatement
+        ``merge_aug_results_kp`` for host ones), NMS on the merged set, the rescale of ``aug_test``;
+        returns (det [k,5], labels [k], kpts [k,3K])"""
+        from .postprocess import aug_merge_kp, aug_nms_kp, aug_scale_factor
+        metas = [m[0] for m in img_metas]
+        for m in metas:
+            aug_scale_factor(m)                     # NotImplementedError for a per-axis scale factor
+        merge = aug_merge_kp if cands[0][0].is_cuda else merge_aug_results_kp
+        bboxes, scores, kpts = merge([c[0] for c in cands], [c[1] for c in cands], [c[2] for c in cands], metas)
+        det, labels, kp = aug_nms_kp(bboxes, scores, kpts.reshape(kpts.shape[0], -1), self.test_cfg)
+        return rescale_aug_detections(det, labels, kp, metas[0], rescale)
+
     def aug_test(self, imgs, img_metas, rescale=False):
-        raise NotImplementedError
+        """test-time augmentation: ``imgs`` A tensors [1,3,H_a,W_a], ``img_metas`` A lists of one meta (``flip``,
+        ``scale_factor``, ``img_shape``, ``flip_indices``).  Each augmentation is decoded in its own frame, mapped back to
+        the original image, all of them are merged and go through the test_cfg's NMS together; the result has the format
+        of ``simple_test``."""
+        det, labels, kp = self.merge_aug_detections(self.aug_candidates(imgs, img_metas), img_metas, rescale)
+        return self.bbox2result_kp(det, labels, kp, self.bbox_head.num_classes)
 
     def forward_test(self, imgs, img_metas, **kwargs):
         for var, name in [(imgs, 'imgs'), (img_metas, 'img_metas')]:
@@ -207,3 +244,40 @@ class RepPointsDetectorKp(nn.Module):
         if return_loss:
             return self.forward_train(img, img_meta, **kwargs)
         return self.forward_test(img, img_meta, **kwargs)
+
+
+def merge_aug_results_kp(aug_bboxes, aug_scores, aug_kpts, img_metas):
+    """The pure-torch statement of the test-time merge (upstream ``merge_aug_results`` + ``bbox_mapping_back``,
+    mmdet/core/bbox/transforms.py:71-103, with the landmarks carried through); any device.
+
+    Per augmentation (meta: ``img_shape``, scalar ``scale_factor`` s, ``flip``, ``flip_indices``): a flip maps
+    x1' = (w - x2) - 1, x2' = (w - x1) - 1 and every landmark x' = (w - x) - 1 with w = img_shape[1], and moves the landmark
+    in slot k to slot perm[k], perm = flip_indices[0::2] // 2; then box coordinates and landmark x, y are divided by s.
+    Visibility and scores are unchanged.  The rows are concatenated in augmentation order.
+    aug_bboxes [n,4], aug_scores [n,1+C], aug_kpts [n,K,3] per augmentation -> (bboxes [T,4], scores [T,1+C], kpts [T,K,3])."""
+    from .postprocess import aug_scale_factor, flip_perm
+    out_b, out_k = [], []
+    for bboxes, kpts, meta in zip(aug_bboxes, aug_kpts, img_metas):
+        sf = aug_scale_factor(meta)
+        if kpts.dim() == 2:
+            kpts = kpts.reshape(kpts.shape[0], kpts.shape[1] // 3, 3)
+        if meta['flip']:
+            w = float(meta['img_shape'][1])
+            bboxes = torch.stack([(w - bboxes[:, 2]) - 1, bboxes[:, 1], (w - bboxes[:, 0]) - 1, bboxes[:, 3]], dim=1)
+            kpts = kpts[:, flip_perm(meta['flip_indices'], kpts.device)]
+            kpts = torch.stack([(w - kpts[..., 0]) - 1, kpts[..., 1], kpts[..., 2]], dim=-1)
+        out_b.append(bboxes / sf)
+        out_k.append(torch.cat([kpts[..., :2] / sf, kpts[..., 2:]], dim=-1))
+    return torch.cat(out_b), torch.cat(list(aug_scores)), torch.cat(out_k)
+
+
+def rescale_aug_detections(det, labels, kpts, meta, rescale):
+    """the last step of ``aug_test``: merged detections stay in the original frame when ``rescale``, otherwise box
+    coordinates and landmark x, y are multiplied by the first augmentation's scale factor (reppoints_detector.py:74-78)"""
+    if rescale:
+        return det, labels, kpts
+    from .postprocess import aug_scale_factor
+    sf = aug_scale_factor(meta)
+    k = kpts.reshape(kpts.shape[0], -1, 3)
+    k = torch.cat([k[..., :2] * sf, k[..., 2:]], dim=-1).reshape(kpts.shape)
+    return torch.cat([det[:, :4] * sf, det[:, 4:]], dim=1), labels, k

@@ -103,7 +103,8 @@ def multiclass_nms_kp_fused(bboxes, scores, kpts, score_thr, iou_thr, max_num):
     bboxes [B,N,4], scores [B,N,C] (foreground classes only), kpts [B,N,K] float32 on the GPU.
     Returns fixed-size device tensors (det [B,M,5], labels [B,M] int64 0-based, kpts [B,M,K], count [B] int64),
     rows past ``count[b]`` zero; ``M = max_num``.  Raises NotImplementedError beyond the on-chip limits
-    (N <= 4096, N*C <= 16384) -- callers fall back to ``multiclass_nms_kp_batched``."""
+    (``multiclass_nms_fused_supported``: N <= 4096, C <= 64, C * min(N, max_num) <= 16384) -- callers fall back to
+    ``multiclass_nms_kp_batched``."""
     import ctypes
     from . import _lib
     B, N, C = scores.shape
@@ -125,6 +126,12 @@ def multiclass_nms_kp_fused(bboxes, scores, kpts, score_thr, iou_thr, max_num):
     out_k = torch.gather(k, 1, src.unsqueeze(-1).expand(B, max_num, k.shape[-1]))
     out_k = out_k * (torch.arange(max_num, device=count.device).unsqueeze(0) < count.unsqueeze(1)).unsqueeze(-1)
     return det, label, out_k, count
+
+
+def multiclass_nms_fused_supported(B, N, C, max_num):
+    """the library's own statement of the fused hard-NMS limits (csrc/nms.hip kgdet_multiclass_nms_supported)"""
+    from . import _lib
+    return bool(_lib.lib().kgdet_multiclass_nms_supported(int(B), int(N), int(C), int(max_num)))
 
 
 _SOFT_METHODS = {'linear': 1, 'gaussian': 2}      # (nms_wrapper.py:66-68; anything else is the reference's ValueError)
@@ -171,3 +178,94 @@ def multiclass_soft_nms_kp_fused(bboxes, scores, kpts, score_thr, nms_cfg, max_n
     out_k = torch.gather(k, 1, src.unsqueeze(-1).expand(B, max_num, k.shape[-1]))
     out_k = out_k * (torch.arange(max_num, device=count.device).unsqueeze(0) < count.unsqueeze(1)).unsqueeze(-1)
     return det, label, out_k, count
+
+
+# ----------------------------------------------------------------------------------------------
+# test-time augmentation (RepPointsDetectorKp.aug_test)
+# ----------------------------------------------------------------------------------------------
+_perm_cache = {}
+
+
+def flip_perm(flip_indices, device):
+    """the dataset's ``flip_indices`` over interleaved (x, y) channels -> the landmark permutation
+    ``flip_indices[0::2] // 2`` as an int64 tensor on ``device`` (cached per flip_indices and device)"""
+    import numpy as np
+    fi = np.asarray(flip_indices, dtype=np.int64).reshape(-1)
+    key = (str(device), fi.tobytes())
+    perm = _perm_cache.get(key)
+    if perm is None:
+        p = fi[0::2] // 2
+        if not np.array_equal(np.sort(p), np.arange(p.shape[0])) or not np.array_equal(p[p], np.arange(p.shape[0])):
+            raise ValueError('flip_indices do not describe a left/right swap of the landmarks (an involution)')
+        perm = torch.from_numpy(p).to(device)
+        _perm_cache[key] = perm
+    return perm
+
+
+def aug_scale_factor(meta):
+    """an augmentation's scalar scale factor; a per-axis one (keep_ratio=False) is not supported at test time"""
+    import numpy as np
+    sf = meta['scale_factor']
+    if np.ndim(sf) != 0:
+        raise NotImplementedError('test-time augmentation needs a scalar scale_factor (keep_ratio=True); got %r' % (sf, ))
+    return float(sf)
+
+
+def aug_merge_kp(aug_bboxes, aug_scores, aug_kpts, img_metas):
+    """``detector.merge_aug_results_kp`` on the GPU in ONE launch (csrc/aug_merge.hip ``kgdet_aug_merge``): A <= 16
+    augmentations' candidates -- bboxes [n,4], scores [n,1+C], kpts [n,K,3] per augmentation, in its resized frame --
+    mapped back to the original frame (flip undone, divided by the scale factor) and concatenated in augmentation order.
+    Returns (bboxes [T,4], scores [T,1+C], kpts [T,K,3]); bit-identical to the restatement on the same device."""
+    import ctypes
+    from . import _lib
+    A = len(aug_bboxes)
+    assert A == len(aug_scores) == len(aug_kpts) == len(img_metas) and A > 0
+    dev = aug_bboxes[0].device
+    S = aug_scores[0].shape[1]
+    K = aug_kpts[0].shape[1] if aug_kpts[0].dim() == 3 else aug_kpts[0].shape[1] // 3
+    boxes = [b.contiguous().float() for b in aug_bboxes]
+    scores = [s.contiguous().float() for s in aug_scores]
+    kpts = [k.reshape(k.shape[0], K, 3).contiguous().float() for k in aug_kpts]
+    segs = (_lib.AugSegment * A)()
+    perm = None
+    for a, meta in enumerate(img_metas):
+        n = boxes[a].shape[0]
+        assert scores[a].shape == (n, S) and kpts[a].shape == (n, K, 3)
+        segs[a] = _lib.AugSegment(boxes[a].data_ptr(), scores[a].data_ptr(), kpts[a].data_ptr(), n,
+                                  float(meta['img_shape'][1]), aug_scale_factor(meta), 1 if meta['flip'] else 0)
+        if meta['flip'] and perm is None:
+            perm = flip_perm(meta['flip_indices'], dev).to(torch.int32)
+            assert perm.shape[0] == K, 'flip_indices cover %d landmarks, the head predicts %d' % (perm.shape[0], K)
+    T = sum(b.shape[0] for b in boxes)
+    out_b = torch.empty((T, 4), dtype=torch.float32, device=dev)
+    out_s = torch.empty((T, S), dtype=torch.float32, device=dev)
+    out_k = torch.empty((T, K, 3), dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().kgdet_aug_merge(segs, ctypes.c_int32(A), ctypes.c_int32(S), ctypes.c_int32(K), _lib.ptr(perm),
+                                          _lib.ptr(out_b), _lib.ptr(out_s), _lib.ptr(out_k), _lib.current_stream()),
+               'kgdet_aug_merge')
+    return out_b, out_s, out_k
+
+
+def aug_nms_kp(bboxes, scores, kpts, cfg):
+    """``multiclass_nms_kp`` (cfg.score_thr, cfg.nms, cfg.max_per_img) on one image's merged TTA candidates, routed to
+    the fastest implementation with the same result: hard NMS fused (no host read before the results) when
+    ``multiclass_nms_fused_supported``, else batched; soft-NMS fused when ``soft_nms_fused_supported``, else the
+    per-class loop.  bboxes [T,4], scores [T,1+C] (column 0 background), kpts [T,3K].
+    Returns (det [k,5], labels [k], kpts [k,3K])."""
+    T, C = scores.shape[0], scores.shape[1] - 1
+    nms_type = cfg.nms.get('type', 'nms')
+    max_num = cfg.max_per_img
+    if bboxes.is_cuda and max_num > 0 and T > 0:
+        if nms_type == 'nms' and multiclass_nms_fused_supported(1, T, C, max_num):
+            det, label, kp, count = multiclass_nms_kp_fused(bboxes[None], scores[None, :, 1:], kpts[None], cfg.score_thr,
+                                                            float(cfg.nms['iou_thr']), max_num)
+        elif nms_type == 'soft_nms' and soft_nms_fused_supported(1, T, C, max_num):
+            det, label, kp, count = multiclass_soft_nms_kp_fused(bboxes[None], scores[None, :, 1:], kpts[None],
+                                                                 cfg.score_thr, cfg.nms, max_num)
+        elif nms_type == 'nms':
+            return multiclass_nms_kp_batched(bboxes[None], scores[None], kpts[None], cfg.score_thr, cfg.nms, max_num)[0]
+        else:
+            return multiclass_nms_kp(bboxes, scores, kpts, cfg.score_thr, cfg.nms, max_num)
+        n = int(count[0])
+        return det[0, :n], label[0, :n], kp[0, :n]
+    return multiclass_nms_kp(bboxes, scores, kpts, cfg.score_thr, cfg.nms, max_num)
