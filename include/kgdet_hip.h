@@ -621,6 +621,33 @@ typedef struct kgdet_aug_segment {
 } kgdet_aug_segment;
 int kgdet_aug_merge(const kgdet_aug_segment *segs, int32_t A, int32_t score_stride, int32_t K, const int32_t *kpt_perm,
                     float *out_boxes, float *out_scores, float *out_kpts, void *stream);
+/* Image preprocessing (datasets.ImageTransform on the device; kgdet_amd/preprocess.py): n_jobs <= KGDET_PREPROC_MAX_JOBS
+ * jobs in ONE launch, the table passed by value (capturable, no host read).  A job resizes one raw uint8 H x W x 3 image
+ * (interleaved, as decoded) to new_h x new_w -- bilinear, half-pixel centres, edge-clamped, no antialias, evaluated in fp32
+ * WITHOUT contraction and rounded half-to-even to a grey level q -- writes norm_lut[c][q] (c the OUTPUT channel; the host
+ * fills the table with (float32(q) - mean[c]) / std[c]) into its [3, out_h, out_w] float32 slot, mirrored left-right
+ * inside the new_w columns when `flip`, and writes 0.0f to every slot element outside new_h x new_w (the slot may be a
+ * reused buffer).  reverse_channels != 0: output channel c reads source channel 2 - c (to_rgb=False).  Per axis, with d the
+ * index in the un-flipped resized image: src = max(scale * (d + 0.5f) - 0.5f, 0), i0 = min((int)src, n - 1),
+ * i1 = i0 + (i0 < n - 1), l1 = src - i0, l0 = 1 - l1; v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d).
+ * Bit-exact against kgdet_amd/preprocess.py::image_transform_restatement.  Several jobs may read one source.  The last
+ * destination dimension is contiguous; rows are stored 16 bytes at a time where dst, the strides and x allow.
+ * n_jobs == 0 is a no-op; n_jobs > KGDET_PREPROC_MAX_JOBS returns KGDET_E_UNSUPPORTED (the caller splits); a null
+ * pointer, a non-positive size, out < new, a row pitch / stride that does not hold its row return KGDET_E_SHAPE. */
+#define KGDET_PREPROC_MAX_JOBS 32
+typedef struct kgdet_preproc_job {
+  const uint8_t *src;                      /* device, H x W x 3 interleaved, as decoded (RGB) */
+  int32_t src_h, src_w, src_row_bytes;     /* row pitch >= 3 * src_w */
+  float *dst;                              /* device, channel 0 of this job's [3, out_h, out_w] slot */
+  int64_t dst_channel_stride;              /* elements */
+  int32_t dst_row_stride;                  /* elements */
+  int32_t new_h, new_w;                    /* resized size = img_shape */
+  int32_t out_h, out_w;                    /* slot size = pad_shape or the batch's common size; zero-filled beyond new_h / new_w */
+  float scale_y, scale_x;                  /* float32(src_h) / new_h, float32(src_w) / new_w, computed by the host in float32 */
+  int32_t flip;                            /* horizontal, applied to the resized image (before padding) */
+} kgdet_preproc_job;
+int kgdet_image_preprocess(const kgdet_preproc_job *jobs, int32_t n_jobs, const float *norm_lut /* device [3][256] */,
+                           int32_t reverse_channels, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

@@ -42,6 +42,18 @@ class AugSegment(ctypes.Structure):
                 ('img_w', ctypes.c_float), ('scale', ctypes.c_double), ('flip', ctypes.c_int32)]
 
 
+PREPROC_MAX_JOBS = 32   # KGDET_PREPROC_MAX_JOBS
+
+
+class PreprocJob(ctypes.Structure):
+    """kgdet_preproc_job (one raw image -> one [3, out_h, out_w] slot of the detector's input)"""
+    _fields_ = [('src', ctypes.c_void_p), ('src_h', ctypes.c_int32), ('src_w', ctypes.c_int32),
+                ('src_row_bytes', ctypes.c_int32), ('dst', ctypes.c_void_p), ('dst_channel_stride', ctypes.c_int64),
+                ('dst_row_stride', ctypes.c_int32), ('new_h', ctypes.c_int32), ('new_w', ctypes.c_int32),
+                ('out_h', ctypes.c_int32), ('out_w', ctypes.c_int32), ('scale_y', ctypes.c_float),
+                ('scale_x', ctypes.c_float), ('flip', ctypes.c_int32)]
+
+
 def build(force=False):
     """Compile every HIP source for gfx950 into kgdet_amd/libkgdet_hip.so (hipcc, in-tree)."""
     cmd = ['make', '-C', CSRC, '-j8']

@@ -15,6 +15,12 @@ Decoding uses PIL (RGB) where the reference uses cv2 (BGR + ``to_rgb``); the res
 centres and no antialiasing (cv2.INTER_LINEAR geometry) evaluated in float and rounded to uint8, which can differ
 from cv2's 11-bit fixed-point result by one grey level.  The reference cannot be run here (no mmcv / cv2), so this
 part is pinned by closed-form cases in tests/test_datasets.py, not by reference outputs.
+
+``ImageTransform`` is the host path and the default.  ``prepare_test_raw`` / ``prepare_train_raw`` / ``collate_device``
+hand the raw uint8 pixels and the planned geometry to ``kgdet_amd.preprocess.DeviceImageTransform`` instead, which does the
+same resize, normalisation, flip and padding for a whole batch in one HIP launch on the GPU (identical geometry and
+normalisation; its resize is defined by ``preprocess.image_transform_restatement`` and differs from the host path by one
+grey level at rounding ties).  Boxes and landmarks are transformed on the host either way.
 """
 import math
 import os
@@ -241,6 +247,60 @@ class DeepFashion2Dataset(object):
                 metas.append(self._meta(info, img_shape, pad_shape, sf, flip))
         return dict(img=imgs, img_meta=metas)
 
+    def _plan(self, img, scale):
+        from .preprocess import plan
+        return plan(img.shape[0], img.shape[1], scale, self.resize_keep_ratio, self.size_divisor)
+
+    def prepare_train_raw(self, idx, img=None):
+        """``prepare_train_img`` without the pixel work: ``raw`` (the decoded uint8 H x W x 3 image), the drawn ``scale`` and
+        ``flip`` (the same draws from numpy's global RNG, in the same order), ``keep_ratio``, the planned ``img_meta`` and
+        the transformed ground truth -- a sample for ``collate_device``."""
+        info = self.img_infos[idx]
+        img = self.load_image(idx) if img is None else img
+        ann = self.get_ann_info(idx)
+        if len(ann['bboxes']) == 0 and self.skip_img_without_anno:
+            return None
+        flip = bool(np.random.rand() < self.flip_ratio)
+        scale = self._sample_scale()
+        _, _, img_shape, pad_shape, sf = self._plan(img, scale)
+        data = dict(raw=torch.from_numpy(np.ascontiguousarray(img)), scale=scale, flip=flip,
+                    keep_ratio=self.resize_keep_ratio, img_meta=self._meta(info, img_shape, pad_shape, sf, flip),
+                    gt_bboxes=torch.from_numpy(bbox_transform(ann['bboxes'], img_shape, sf, flip)))
+        if self.with_label:
+            data['gt_labels'] = torch.from_numpy(ann['labels'])
+        if self.with_crowd:
+            data['gt_bboxes_ignore'] = torch.from_numpy(bbox_transform(ann['bboxes_ignore'], img_shape, sf, flip))
+        if self.with_keypoint:
+            kps = keypoint_transform(ann['keypoints'], img_shape, ann['labels'], sf, self.flip_pairs, flip)
+            if self.group_mode:
+                for inst in kps:
+                    for group in self.keypoint_groups:
+                        vis = inst[group, 2] > 0
+                        if vis.sum() > 0:
+                            inst[group, :] = inst[group, :][np.tile(vis[:, None], (1, 3))]
+            data['gt_keypoints'] = torch.from_numpy(kps.astype(np.float32))
+        return data
+
+    def prepare_test_raw(self, idx, img=None):
+        """``prepare_test_img`` without the pixel work: ``raw`` (uint8 H x W x 3) once, and per augmentation -- in
+        ``prepare_test_img``'s order -- its ``scales`` / ``flips`` entry and planned ``img_meta``"""
+        info = self.img_infos[idx]
+        img = self.load_image(idx) if img is None else img
+        scales, flips, metas = [], [], []
+        for scale in self.img_scales:
+            for flip in ([False, True] if self.flip_ratio > 0 else [False]):
+                _, _, img_shape, pad_shape, sf = self._plan(img, scale)
+                scales.append(scale)
+                flips.append(flip)
+                metas.append(self._meta(info, img_shape, pad_shape, sf, flip))
+        return dict(raw=torch.from_numpy(np.ascontiguousarray(img)), scales=scales, flips=flips,
+                    keep_ratio=self.resize_keep_ratio, img_meta=metas)
+
+    def device_transform(self, device=None):
+        """the ``DeviceImageTransform`` with this dataset's normalisation and ``size_divisor``"""
+        from .preprocess import DeviceImageTransform
+        return DeviceImageTransform(size_divisor=self.size_divisor, device=device, **self.img_norm_cfg)
+
     def __getitem__(self, idx):
         if self.test_mode:
             return self.prepare_test_img(idx)
@@ -263,6 +323,21 @@ def collate(batch):
     for key in batch[0]:
         if key not in ('img', 'img_meta'):
             out[key] = [b[key] for b in batch]
+    return out
+
+
+def collate_device(samples, transform):
+    """``collate`` for ``prepare_train_raw`` samples: the same batch dict, with ``img`` [B, 3, H, W] made on the GPU by ONE
+    launch of ``transform`` (a ``preprocess.DeviceImageTransform``) at the batch's common size; everything else stays
+    per-image lists of host tensors.  ``Runner.train_epoch(loader, to_device=...)`` moves those as before."""
+    keep_ratio = samples[0]['keep_ratio']
+    assert all(s['keep_ratio'] == keep_ratio for s in samples)
+    img, _ = transform([s['raw'] for s in samples], [s['scale'] for s in samples], [s['flip'] for s in samples],
+                       keep_ratio=keep_ratio, common_size=True)
+    out = dict(img=img, img_meta=[s['img_meta'] for s in samples])
+    for key in samples[0]:
+        if key not in ('raw', 'scale', 'flip', 'keep_ratio', 'img_meta'):
+            out[key] = [s[key] for s in samples]
     return out
 
 

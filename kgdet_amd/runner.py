@@ -144,11 +144,14 @@ def test_shard(n, world_size, rank):
     return idx[rank:total:world_size]
 
 
-def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1):
+def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False):
     """results of the samples ``indices`` in that order.  imgs_per_gpu == 1: the reference's call, one image per forward
     (``model(return_loss=False, rescale=..., **data)``, tools/test.py:25-28); > 1: runs of consecutive samples with identical
     tensor shapes and one augmentation go through ``simple_test_batch`` together (the same per-image results: nothing in
-    backbone / neck / head / decode / NMS mixes the images of a batch)."""
+    backbone / neck / head / decode / NMS mixes the images of a batch).  ``device_preprocess``: the input transform runs on the
+    model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then)."""
+    if device_preprocess:
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
@@ -178,9 +181,44 @@ def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1):
     return results
 
 
-def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1):
-    """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order"""
-    return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu)
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1):
+    """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
+    planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
+    ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
+    tensor shapes ARE the pad shapes), one launch for all augmentations of a TTA sample (its raw image uploaded once)."""
+    model.eval()
+    transform = dataset.device_transform(next(model.parameters()).device)
+    results, i = [], 0
+    carried = None
+    while i < len(indices):
+        data = carried if carried is not None else dataset.prepare_test_raw(indices[i])
+        carried = None
+        group = [data]
+        while (imgs_per_gpu > 1 and len(group) < imgs_per_gpu and i + len(group) < len(indices)
+               and len(data['img_meta']) == 1):
+            nxt = dataset.prepare_test_raw(indices[i + len(group)])
+            if len(nxt['img_meta']) != 1 or nxt['img_meta'][0]['pad_shape'] != data['img_meta'][0]['pad_shape']:
+                carried = nxt
+                break
+            group.append(nxt)
+        with torch.no_grad():
+            if len(group) == 1:
+                imgs, _ = transform.separate([data['raw']] * len(data['scales']), data['scales'], data['flips'],
+                                             keep_ratio=data['keep_ratio'])
+                results.append(model(imgs, [[m] for m in data['img_meta']], return_loss=False, rescale=rescale))
+            else:
+                img, _ = transform([g['raw'] for g in group], [g['scales'][0] for g in group],
+                                   [g['flips'][0] for g in group], keep_ratio=data['keep_ratio'])
+                results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
+        i += len(group)
+    return results
+
+
+def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False):
+    """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
+    resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
+    used then) instead of ``dataset[i]``'s host transform; same result format and order."""
+    return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess)
 
 
 def collect_results(result_part, size, group=None):
@@ -204,13 +242,15 @@ def collect_results(result_part, size, group=None):
     return ordered[:size]
 
 
-def multi_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, group=None):
-    """tools/test.py:38-58: every rank runs its shard of the dataset, rank 0 returns all results in dataset order"""
+def multi_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, group=None, device_preprocess=False):
+    """tools/test.py:38-58: every rank runs its shard of the dataset, rank 0 returns all results in dataset order
+    (``device_preprocess``: as in ``single_gpu_test``, on each rank's own device)"""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if on else 1
     rank = dist.get_rank(group) if on else 0
-    part = _test_on(model, dataset, test_shard(len(dataset), world, rank), rescale, to_device, imgs_per_gpu)
+    part = _test_on(model, dataset, test_shard(len(dataset), world, rank), rescale, to_device, imgs_per_gpu,
+                    device_preprocess)
     return collect_results(part, len(dataset), group)
 
 
@@ -373,6 +413,10 @@ class Runner(object):
         return ckpt
 
     def train_epoch(self, data_loader, to_device=None):
+        """``to_device(data)`` turns what the loader yields into the batch dict on the GPU.  For the device-side input
+        transform let the loader yield lists of ``dataset.prepare_train_raw`` samples and pass
+        ``to_device=lambda samples: move(datasets.collate_device(samples, dataset.device_transform()))`` with ``move``
+        the usual host->device copy of the ground-truth lists (the image is made on the GPU by one launch)."""
         self.model.train()
         self.lr.before_train_epoch(self.optimizer, self.epoch)
         t0 = time.time()
