@@ -648,6 +648,31 @@ typedef struct kgdet_preproc_job {
 } kgdet_preproc_job;
 int kgdet_image_preprocess(const kgdet_preproc_job *jobs, int32_t n_jobs, const float *norm_lut /* device [3][256] */,
                            int32_t reverse_channels, void *stream);
+/* COCO-style bbox / OKS evaluation on the device (evaluation.CocoEvaluator's similarity and matching steps;
+ * kgdet_amd/evaluation_device.py packs the arrays and holds the numpy restatement).  All device pointers; one launch each
+ * over the C (image, category) cells of `cells` int32 [C, 4] = (first detection, detections, first ground truth, ground
+ * truths) into the packed arrays of ND detections (inside a cell in descending-score order) and NG ground truths;
+ * sim_off int64 [C] = where the cell's row-major [D, G] block starts in sim (sim_size doubles).  A cell whose ranges leave
+ * the arrays is skipped.  Coordinates, areas and similarities are float64, evaluated without contraction.
+ * kgdet_coco_similarity: iou_type 0 = box IoU of d_box / g_box [n, 4] xywh, union = the detection's area against a crowd
+ * ground truth (g_crowd int32), bit-identical to evaluation.box_iou_xywh; iou_type 1 = OKS over K landmarks of d_kxy
+ * [ND, K, 2] against g_kpt [NG, K, 3] (x, y, v) with var [K] = (2 sigma)^2: the landmarks with v > 0 (g_nvis int32 [NG] =
+ * their number) or, when there is none, all K by the distance to the doubled g_box; exponent argument
+ * (dx^2 + dy^2) / var / (area + 2^-52) / 2 bit-identical to evaluation.oks, summed over a wave's lanes in a fixed order.
+ * Pointers the chosen type does not read may be NULL.
+ * kgdet_coco_match: the greedy sweep of CocoEvaluator._match for every (area range a < A, threshold t < T), A * T <= 64
+ * (KGDET_E_SHAPE beyond): area_rng [A, 2], best0 [T] = min(threshold, 1 - 1e-10), g_ignore uint8 [NG] = the type's base
+ * flag (crowd; keypoints: no labelled landmark either).  Writes d_match int32 [ND, A, T] = 1 + the packed index of the
+ * matched ground truth or 0, d_ignore uint8 [ND, A, T], g_ignore_out uint8 [NG, A] (in packed order, not sorted);
+ * g_taken uint8 [NG, A, T] is scratch, initialised by the kernel. */
+int kgdet_coco_similarity(int32_t iou_type, const int32_t *cells, const int64_t *sim_off, int32_t C, int64_t ND, int64_t NG,
+                          int64_t sim_size, const double *d_box, const double *d_kxy, const double *g_box,
+                          const double *g_kpt, const double *g_area, const int32_t *g_crowd, const int32_t *g_nvis,
+                          const double *var, int32_t K, double *sim, void *stream);
+int kgdet_coco_match(const int32_t *cells, const int64_t *sim_off, int32_t C, int64_t ND, int64_t NG, int64_t sim_size,
+                     const double *sim, const double *d_area, const double *g_area, const uint8_t *g_ignore,
+                     const int32_t *g_crowd, const double *area_rng, int32_t A, const double *best0, int32_t T,
+                     int32_t *d_match, uint8_t *d_ignore, uint8_t *g_ignore_out, uint8_t *g_taken, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

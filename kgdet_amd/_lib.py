@@ -86,6 +86,11 @@ def lib():
             if hasattr(L, name):
                 getattr(L, name).restype = ctypes.c_int
                 getattr(L, name).argtypes = [ctypes.c_int32] * 4
+        if hasattr(L, 'kgdet_coco_similarity'):      # evaluation_device.py: int64 sizes among the arguments
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_coco_similarity.restype = L.kgdet_coco_match.restype = ctypes.c_int
+            L.kgdet_coco_similarity.argtypes = [i32, vp, vp, i32, i64, i64, i64] + [vp] * 8 + [i32, vp, vp]
+            L.kgdet_coco_match.argtypes = [vp, vp, i32, i64, i64, i64] + [vp] * 6 + [i32, vp, i32] + [vp] * 5
         _lib = L
     return _lib
 

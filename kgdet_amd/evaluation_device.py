@@ -1,0 +1,593 @@
+"""The bbox / landmark (OKS) evaluator on packed arrays, with its two hot steps on the GPU.
+
+``evaluation.CocoEvaluator`` restates pycocotools: dictionaries per annotation, a Python loop per ground truth for the
+similarities and four nested Python loops for the matching.  This module keeps its semantics -- it is held to
+``CocoEvaluator`` value for value by tests/test_eval_packed.py and tests/test_gpu_eval.py -- on a layout a kernel can walk:
+
+* ``pack_ground_truth(coco)``: once per dataset.  Annotations sorted (stably) by cell = (image index, category index) in
+  the sorted id order ``CocoEvaluator`` uses, one float64 / integer array per field, a CSR table ``start`` over all cells.
+* ``pack_results`` (the list-of-dicts form ``CocoIndex.load_results`` takes) / ``pack_test_results`` (what
+  ``single_gpu_test`` returns, no files: ``kpt2json``'s rounding applied to the arrays): detections sorted by cell, inside a
+  cell by descending score (stable), cut to the type's ``max_dets[-1]``.
+* ``DeviceCocoEvaluator``: ``evaluate()`` runs similarity + matching for every cell in one launch each
+  (csrc/coco_eval.hip) or, with ``device='cpu'``, their numpy restatement below; ``accumulate()`` is numpy over the packed
+  outputs, vectorised per (category, area range, max_dets); ``summarize()`` is ``CocoEvaluator``'s.
+
+What the device computes differently from numpy is stated in DESIGN.md: box IoU is bit-identical; for OKS the exponent
+argument is bit-identical, ``exp`` and the order of the sum over the landmarks are the device's.
+"""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+from .evaluation import CocoEvaluator, CocoIndex, EvalParams, landmark_meta
+
+MAX_DETS = dict(bbox=100, keypoints=20)       # EvalParams.max_dets[-1] per type
+# detections per launch: bounds the device (and pinned staging) memory of one chunk -- a landmark detection is 4.7 kB
+CHUNK_DETS = dict(bbox=1 << 22, keypoints=1 << 18)
+
+
+class Packed(object):
+    """a bag of arrays (attributes)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _index_of(sorted_ids, ids):
+    """(position of every id in sorted_ids, whether it is there)"""
+    ids = np.asarray(ids)
+    if len(sorted_ids) == 0:
+        return np.zeros(len(ids), np.int64), np.zeros(len(ids), bool)
+    pos = np.minimum(np.searchsorted(sorted_ids, ids), len(sorted_ids) - 1)
+    return pos.astype(np.int64), sorted_ids[pos] == ids
+
+
+def _csr(cell_sorted, n_cells):
+    return np.searchsorted(cell_sorted, np.arange(n_cells + 1)).astype(np.int64)
+
+
+def pack_ground_truth(coco):
+    """Annotations of a ``CocoIndex`` (or an annotation file / dict) as arrays, in cell order.  Built once per dataset.
+    An annotation id of 0 is refused (``ValueError``): ``CocoEvaluator``, like pycocotools, stores the matched ground truth's id
+    and reads 0 as "unmatched", so a match to such an annotation counts as a miss there; the packed path tells matched from
+    unmatched by index and does not reproduce that -- renumber the annotations, or use ``CocoEvaluator``."""
+    if not isinstance(coco, CocoIndex):
+        coco = CocoIndex(coco)
+    K = len(landmark_meta()['oks_sigmas'])
+    img_ids = np.unique(np.asarray(coco.get_img_ids(), dtype=np.int64))
+    cat_ids = np.unique(np.asarray(coco.get_cat_ids(), dtype=np.int64))
+    anns = list(coco.dataset.get('annotations', ()))
+    ii, ok_i = _index_of(img_ids, np.asarray([a['image_id'] for a in anns], dtype=np.int64))
+    ci, ok_c = _index_of(cat_ids, np.asarray([a['category_id'] for a in anns], dtype=np.int64))
+    keep = np.nonzero(ok_i & ok_c)[0]           # (what get_ann_ids(img_ids, cat_ids) selects)
+    cell = ii[keep] * len(cat_ids) + ci[keep]
+    order = keep[np.argsort(cell, kind='mergesort')]
+    anns = [anns[i] for i in order]
+    n = len(anns)
+    if any(a['id'] == 0 for a in anns):
+        raise ValueError('annotation id 0 reads as "unmatched" in CocoEvaluator; the packed evaluator refuses it')
+    kpt = np.zeros((n, K * 3), np.float64)
+    for r, a in enumerate(anns):
+        if a.get('keypoints'):
+            kpt[r] = a['keypoints']
+    n_vis = np.count_nonzero(kpt[:, 2::3] > 0, axis=1).astype(np.int32)
+    cell = ii[order] * len(cat_ids) + ci[order]
+    return Packed(
+        img_ids=img_ids, cat_ids=cat_ids, num_landmarks=K, img_idx=ii[order], cat_idx=ci[order], cell=cell,
+        start=_csr(cell, len(img_ids) * len(cat_ids)),
+        bbox=np.asarray([a['bbox'] for a in anns], dtype=np.float64).reshape(n, 4),
+        area=np.asarray([a['area'] for a in anns], dtype=np.float64),
+        iscrowd=np.asarray([int(a.get('iscrowd', 0)) for a in anns], dtype=np.int32),
+        num_keypoints=np.asarray([a['num_keypoints'] if 'num_keypoints' in a else v for a, v in zip(anns, n_vis)],
+                                 dtype=np.int64),
+        id=np.asarray([a['id'] for a in anns], dtype=np.int64), keypoints=kpt, num_visible=n_vis)
+
+
+def _order_dets(pg, kind, image_id, category_id, score):
+    """(source rows kept, in packed order; image index; category index) -- by cell, inside a cell by descending score with the
+    input order for equal scores, cut to the type's max_dets[-1]; a category the ground truth does not know is never loaded"""
+    image_id = np.asarray(image_id, dtype=np.int64)
+    ii, ok_i = _index_of(pg.img_ids, image_id)
+    if not ok_i.all():
+        raise ValueError('Results do not correspond to current coco set')
+    ci, ok_c = _index_of(pg.cat_ids, np.asarray(category_id, dtype=np.int64))
+    cell = np.where(ok_c, ii * len(pg.cat_ids) + ci, -1)
+    order = np.lexsort((-score, cell))                             # stable
+    order = order[cell[order] >= 0]
+    first = _csr(cell[order], len(pg.img_ids) * len(pg.cat_ids))
+    rank = np.arange(len(order)) - first[cell[order]]
+    return order[rank < MAX_DETS[kind]], ii, ci
+
+
+def _pack_dets(pg, kind, image_id, category_id, score, bbox, area, kxy, order=None):
+    """``kxy``: [n, K, 2] in input order, or already in packed order when ``order`` (from ``_order_dets``) is passed"""
+    score = np.asarray(score, dtype=np.float64)
+    if order is None:
+        order, ii, ci = _order_dets(pg, kind, image_id, category_id, score)
+        if kxy is not None:
+            kxy = np.ascontiguousarray(kxy[order])
+    else:
+        order, ii, ci = order
+    cell = ii[order] * len(pg.cat_ids) + ci[order]
+    return Packed(kind=kind, cell=cell, start=_csr(cell, len(pg.img_ids) * len(pg.cat_ids)), img_idx=ii[order],
+                  cat_idx=ci[order], score=score[order], bbox=np.ascontiguousarray(bbox[order]), area=area[order],
+                  id=order.astype(np.int64) + 1, kxy=kxy)          # load_results: id = k + 1
+
+
+def _result_kind(first):
+    if 'bbox' in first and first['bbox'] != []:
+        return 'bbox'
+    if 'keypoints' in first:
+        return 'keypoints'
+    raise ValueError('only bbox and keypoints results are supported')
+
+
+def _derive_from_landmarks(kpt):
+    """load_results for a landmark result: bbox / area from the extent of ALL coordinates.  kpt [n, 3K] -> bbox, area, kxy"""
+    n = len(kpt)
+    xy = kpt.reshape(n, -1, 3)[:, :, :2]
+    if n == 0:
+        return np.zeros((0, 4)), np.zeros(0), np.ascontiguousarray(xy)
+    x0, x1, y0, y1 = xy[:, :, 0].min(1), xy[:, :, 0].max(1), xy[:, :, 1].min(1), xy[:, :, 1].max(1)
+    return np.stack([x0, y0, x1 - x0, y1 - y0], axis=1), (x1 - x0) * (y1 - y0), np.ascontiguousarray(xy)
+
+
+def pack_results(packed_gt, results):
+    """Detections in the form ``CocoIndex.load_results`` takes (a list of dicts, or a json file of them) -> packed arrays.
+    The type is the first result's, as there: 'bbox' results get ``area = w * h``, landmark results ``bbox`` / ``area`` from
+    the extent of all 294 coordinates; ids are ``k + 1``.  The dicts are not modified."""
+    if isinstance(results, (str, bytes, os.PathLike)):
+        with open(results) as f:
+            results = json.load(f)
+    if not isinstance(results, list):
+        raise TypeError('results must be a list of objects')
+    K = packed_gt.num_landmarks
+    img = [r['image_id'] for r in results]
+    _, known = _index_of(packed_gt.img_ids, np.asarray(img, dtype=np.int64))
+    if not known.all():
+        raise ValueError('Results do not correspond to current coco set')
+    if not results:
+        return _pack_dets(packed_gt, 'bbox', [], [], [], np.zeros((0, 4)), np.zeros(0), None)
+    kind = _result_kind(results[0])
+    cat = [r['category_id'] for r in results]
+    score = [r['score'] for r in results]
+    if kind == 'bbox':
+        bbox = np.asarray([r['bbox'] for r in results], dtype=np.float64).reshape(len(results), 4)
+        return _pack_dets(packed_gt, kind, img, cat, score, bbox, bbox[:, 2] * bbox[:, 3], None)
+    kpt = np.asarray([r['keypoints'] for r in results], dtype=np.float64).reshape(len(results), K * 3)
+    bbox, area, kxy = _derive_from_landmarks(kpt)
+    return _pack_dets(packed_gt, kind, img, cat, score, bbox, area, kxy)
+
+
+def round_like_python(values, num_digits):
+    """``[round(float(v), num_digits) for v in values]`` as an array.  Python rounds the exact decimal value correctly;
+    ``np.round`` computes ``rint(v * 10**d) / 10**d`` and differs where the product's own rounding crosses a half.  For
+    ``|v * 10**d| < 2**40`` that product is off by at most 2**-13, so wherever its fraction is further than 1e-3 from 0.5 both
+    pick the same integer n, and both return the double nearest to n / 10**d (a correctly rounded division of two exactly
+    represented integers).  Those elements take ``np.round``; the others (about 0.2 %) take Python's ``round``."""
+    v = np.asarray(values, dtype=np.float64)
+    out = np.round(v, num_digits)
+    if num_digits <= 0:
+        risky = np.ones(v.shape, bool)
+    else:
+        s = v * 10.0 ** num_digits
+        with np.errstate(invalid='ignore'):
+            risky = ~(np.abs(s) < 2.0 ** 40) | (np.abs(np.abs(s - np.floor(s)) - 0.5) <= 1e-3)
+    flat, idx = out.reshape(-1), np.nonzero(risky.reshape(-1))[0]
+    src = v.reshape(-1)
+    for i in idx:
+        flat[i] = round(float(src[i]), num_digits)
+    return flat.reshape(v.shape)
+
+
+def _landmarks_in_order(blocks, n, order, K, num_digits, batch=4096):
+    """kpt2json + load_results for the landmark rows of ``blocks`` (arrays [m, 3K] in result order, n rows together):
+    ``np.round(float64, num_digits)``, bbox / area from the extent of all coordinates (for every row, in input order), and the
+    x, y of the rows ``order`` keeps written straight into their packed place -- in batches of rows on a few threads (numpy
+    drops the interpreter lock), so the float64 copy of all 882 values per row never exists at once."""
+    from concurrent.futures import ThreadPoolExecutor
+    pos = np.full(n, -1, np.int64)
+    pos[order] = np.arange(len(order))
+    bbox, area, kxy = np.zeros((n, 4)), np.zeros(n), np.zeros((len(order), K, 2))
+
+    def work(job):
+        r0, parts = job
+        a = np.concatenate(parts).astype(np.float64) if len(parts) > 1 else parts[0].astype(np.float64)
+        np.round(a, num_digits, out=a)
+        v = a.reshape(len(a), K, 3)
+        x0, x1, y0, y1 = v[:, :, 0].min(1), v[:, :, 0].max(1), v[:, :, 1].min(1), v[:, :, 1].max(1)
+        bbox[r0:r0 + len(a)] = np.stack([x0, y0, x1 - x0, y1 - y0], axis=1)
+        area[r0:r0 + len(a)] = (x1 - x0) * (y1 - y0)
+        to = pos[r0:r0 + len(a)]
+        keep = to >= 0
+        kxy[to[keep]] = v[keep, :, :2]
+
+    def jobs():
+        r0, rows, parts = 0, 0, []
+        for blk in blocks:
+            parts.append(blk)
+            rows += len(blk)
+            if rows >= batch:
+                yield r0, parts
+                r0, rows, parts = r0 + rows, 0, []
+        if parts:
+            yield r0, parts
+
+    workers = max(1, min(16, int(os.environ.get('OMP_NUM_THREADS') or 4)))
+    with ThreadPoolExecutor(workers) as pool:
+        pending = []
+        for job in jobs():                       # (a bounded queue: the batches' float64 copies are the memory in flight)
+            pending.append(pool.submit(work, job))
+            if len(pending) >= 2 * workers:
+                pending.pop(0).result()
+        for f in pending:
+            f.result()
+    return bbox, area, kxy
+
+
+def pack_test_results(packed_gt, dataset, results, num_digits=4):
+    """{'bbox': packed[, 'keypoints': packed]} straight from what ``single_gpu_test`` / ``multi_gpu_test`` return, with the very
+    numbers ``results2json`` + ``json.dump`` + ``load_results`` yield (a float's json text reads back as the same float):
+    ``det2json`` for per-class box lists (no rounding), ``kpt2json`` for (boxes, scores, landmarks) tuples --
+    ``np.round(float64, num_digits)`` for the landmarks, Python's ``round`` for xywh and the score (``round_like_python``)."""
+    if not isinstance(results[0], (list, tuple)):
+        raise TypeError('invalid type of results')
+    with_kpt = isinstance(results[0], tuple)
+    K = packed_gt.num_landmarks
+    rows, kpts, img, cat = [], [], [], []
+    for idx in range(len(dataset)):
+        res = results[idx]
+        if with_kpt:
+            if len(res) != 3:
+                continue
+            det, kpt = res[0], res[2]
+        else:
+            det, kpt = res, None
+        for label in range(len(det)):
+            boxes = np.asarray(det[label]).reshape(-1, 5)
+            if kpt is not None:
+                pts = np.asarray(kpt[label]).reshape(len(kpt[label]), K * 3)
+                if len(pts) != len(boxes):
+                    raise ValueError('image %d, class %d: %d boxes but %d landmark rows' % (idx, label, len(boxes), len(pts)))
+                if len(pts):
+                    kpts.append(pts)
+            if len(boxes):
+                rows.append(boxes.astype(np.float64))
+                img.append(np.full(len(boxes), dataset.img_ids[idx], dtype=np.int64))
+                cat.append(np.full(len(boxes), dataset.cat_ids[label], dtype=np.int64))
+    rows = np.concatenate(rows) if rows else np.zeros((0, 5))
+    img = np.concatenate(img) if img else np.zeros(0, np.int64)
+    cat = np.concatenate(cat) if cat else np.zeros(0, np.int64)
+    xywh = np.stack([rows[:, 0], rows[:, 1], rows[:, 2] - rows[:, 0] + 1, rows[:, 3] - rows[:, 1] + 1], axis=1)
+    score = rows[:, 4]
+    if with_kpt:
+        xywh, score = round_like_python(xywh, num_digits), round_like_python(score, num_digits)
+    out = dict(bbox=_pack_dets(packed_gt, 'bbox', img, cat, score, xywh, xywh[:, 2] * xywh[:, 3], None))
+    if with_kpt:
+        order = _order_dets(packed_gt, 'keypoints', img, cat, score)
+        bbox, area, kxy = _landmarks_in_order(kpts, len(rows), order[0], K, num_digits)
+        out['keypoints'] = _pack_dets(packed_gt, 'keypoints', img, cat, score, bbox, area, kxy, order=order)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the two kernels restated in numpy on the packed layout (csrc/coco_eval.hip)
+# ------------------------------------------------------------------------------------------------
+def similarity_restatement(c):
+    """``kgdet_coco_similarity`` for one chunk ``c`` (see ``DeviceCocoEvaluator._chunks``): evaluation.box_iou_xywh /
+    evaluation.oks, operation by operation, on the arrays."""
+    sim = np.zeros(c.sim_size, np.float64)
+    for (d0, D, g0, G), off in zip(c.cells, c.sim_off):
+        if D == 0 or G == 0:
+            continue
+        if c.iou_type == 'bbox':
+            d, g = c.d_box[d0:d0 + D], c.g_box[g0:g0 + G]
+            iw = np.minimum(d[:, None, 0] + d[:, None, 2], g[None, :, 0] + g[None, :, 2]) - np.maximum(d[:, None, 0], g[None, :, 0])
+            ih = np.minimum(d[:, None, 1] + d[:, None, 3], g[None, :, 1] + g[None, :, 3]) - np.maximum(d[:, None, 1], g[None, :, 1])
+            inter = np.where((iw > 0) & (ih > 0), iw * ih, 0.0)
+            da, ga = (d[:, 2] * d[:, 3])[:, None], (g[:, 2] * g[:, 3])[None, :]
+            union = np.where(c.g_crowd[g0:g0 + G].astype(bool)[None, :], da, da + ga - inter)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                block = np.where(inter > 0, inter / union, 0.0)
+        else:
+            xd, yd = c.d_kxy[d0:d0 + D, :, 0], c.d_kxy[d0:d0 + D, :, 1]
+            block = np.zeros((D, G))
+            for j in range(G):
+                k = c.g_kpt[g0 + j]
+                xg, yg, vis = k[0::3], k[1::3], k[2::3] > 0
+                if c.g_nvis[g0 + j] > 0:
+                    dx, dy = xd - xg, yd - yg
+                else:
+                    bx, by, bw, bh = c.g_box[g0 + j]
+                    x0, x1, y0, y1 = bx - bw, bx + bw * 2, by - bh, by + bh * 2
+                    dx = np.maximum(0, x0 - xd) + np.maximum(0, xd - x1)
+                    dy = np.maximum(0, y0 - yd) + np.maximum(0, yd - y1)
+                e = (dx ** 2 + dy ** 2) / c.var / (c.g_area[g0 + j] + np.spacing(1)) / 2
+                if c.g_nvis[g0 + j] > 0:
+                    e = e[:, vis]
+                block[:, j] = np.exp(-e).sum(axis=1) / e.shape[1]
+        sim[off:off + D * G] = block.reshape(-1)
+    return sim
+
+
+def match_restatement(c, sim):
+    """``kgdet_coco_match`` for one chunk: every (area range, threshold) pair is a lane ([A, T] arrays), a detection sweeps the
+    regular ground truths in order and then, in the lanes where none matched, the ignored ones."""
+    A, T = len(c.area_rng), len(c.best0)
+    lo, hi = c.area_rng[:, 0], c.area_rng[:, 1]
+    d_match = np.zeros((c.nd, A, T), np.int32)
+    d_ignore = np.zeros((c.nd, A, T), np.uint8)
+    g_ignore = np.zeros((c.ng, A), np.uint8)
+    aa, tt = np.meshgrid(np.arange(A), np.arange(T), indexing='ij')
+    for (d0, D, g0, G), off in zip(c.cells, c.sim_off):
+        ga = c.g_area[g0:g0 + G]
+        ign = c.g_ign[g0:g0 + G, None].astype(bool) | (ga[:, None] < lo[None]) | (ga[:, None] > hi[None])     # [G, A]
+        g_ignore[g0:g0 + G] = ign
+        ign = np.repeat(ign[:, :, None], T, axis=2)
+        taken = np.zeros((G, A, T), bool)
+        crowd = c.g_crowd[g0:g0 + G] != 0
+        block = sim[off:off + D * G].reshape(D, G) if D and G else None
+        for di in range(D):
+            best = np.broadcast_to(c.best0[None, :], (A, T)).copy()
+            m = np.full((A, T), -1)
+            if block is not None:
+                for sweep in (False, True):
+                    live = (m < 0) if sweep else np.ones((A, T), bool)
+                    for gi in range(G):
+                        cand = live & (ign[gi] == sweep) & ~(taken[gi] & ~crowd[gi]) & ~(block[di, gi] < best)
+                        best = np.where(cand, block[di, gi], best)
+                        m = np.where(cand, gi, m)
+            hit = m >= 0
+            da = c.d_area[d0 + di]
+            outside = np.broadcast_to(((da < lo) | (da > hi))[:, None], (A, T))
+            d_ignore[d0 + di] = np.where(hit, ign[np.maximum(m, 0), aa, tt] if G else False, outside)
+            d_match[d0 + di] = np.where(hit, g0 + m + 1, 0)
+            taken[m[hit], aa[hit], tt[hit]] = True
+    return d_match, d_ignore, g_ignore
+
+
+def _run_host(c, want_sim=True):
+    sim = similarity_restatement(c)
+    return (sim if want_sim else None,) + match_restatement(c, sim)
+
+
+def _run_device(c, device, want_sim=True):
+    """the two launches of csrc/coco_eval.hip for one chunk; the similarity matrix stays on the device between them"""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    dev = torch.device(device)
+
+    def up(a, dtype=None):
+        if a is None:
+            return None
+        t = torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype, copy=False)))
+        return t.to(dev, non_blocking=False)
+
+    A, T = len(c.area_rng), len(c.best0)
+    kp = c.iou_type == 'keypoints'
+    with torch.cuda.device(dev):
+        cells, sim_off = up(c.cells, np.int32), up(c.sim_off, np.int64)
+        d_box, g_box = (None if kp else up(c.d_box)), up(c.g_box)
+        d_kxy, g_kpt = (up(c.d_kxy), up(c.g_kpt)) if kp else (None, None)
+        d_area, g_area = up(c.d_area), up(c.g_area)
+        g_crowd, g_nvis, g_ign = up(c.g_crowd, np.int32), up(c.g_nvis, np.int32), up(c.g_ign, np.uint8)
+        var, rng, best0 = up(c.var), up(c.area_rng), up(c.best0)
+        sim = torch.zeros(max(c.sim_size, 1), dtype=torch.float64, device=dev)
+        d_match = torch.zeros((c.nd, A, T), dtype=torch.int32, device=dev)
+        d_ignore = torch.zeros((c.nd, A, T), dtype=torch.uint8, device=dev)
+        g_ignore = torch.zeros((c.ng, A), dtype=torch.uint8, device=dev)
+        g_taken = torch.empty((c.ng, A, T), dtype=torch.uint8, device=dev)
+        stream, p = _lib.current_stream(), _lib.ptr
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        C = len(c.cells)
+        _lib.check(L.kgdet_coco_similarity(i32(1 if kp else 0), p(cells), p(sim_off), i32(C), i64(c.nd), i64(c.ng),
+                                           i64(c.sim_size), p(d_box), p(d_kxy), p(g_box), p(g_kpt), p(g_area), p(g_crowd),
+                                           p(g_nvis), p(var), i32(len(c.var)), p(sim), stream), 'kgdet_coco_similarity')
+        _lib.check(L.kgdet_coco_match(p(cells), p(sim_off), i32(C), i64(c.nd), i64(c.ng), i64(c.sim_size), p(sim), p(d_area),
+                                      p(g_area), p(g_ign), p(g_crowd), p(rng), i32(A), p(best0), i32(T), p(d_match),
+                                      p(d_ignore), p(g_ignore), p(g_taken), stream), 'kgdet_coco_match')
+        return (sim[:c.sim_size].cpu().numpy() if want_sim else None, d_match.cpu().numpy(), d_ignore.cpu().numpy(),
+                g_ignore.cpu().numpy())
+
+
+def _default_device():
+    from . import _lib
+    try:
+        import torch
+        if torch.cuda.is_available() and os.path.exists(_lib.LIB_PATH):
+            return 'cuda'
+    except ImportError:
+        pass
+    return 'cpu'
+
+
+class DeviceCocoEvaluator(CocoEvaluator):
+    """``CocoEvaluator`` on packed arrays.  ``device``: a CUDA device (the HIP kernels), ``'cpu'`` (their numpy restatement)
+    or None = the GPU when there is one and the library is built, else the restatement.  ``params`` as ``CocoEvaluator``'s;
+    what packing has already fixed cannot be edited there: ``evaluate`` raises ``ValueError`` when ``img_ids`` / ``cat_ids`` are
+    not the packed ground truth's (pack a subset instead), when ``max_dets[-1]`` is not the cut the detections were packed
+    with, and for ``use_cats = 0``.  ``iou_thrs``, ``rec_thrs``, ``area_rng`` (at most 64 (range, threshold) pairs) and the
+    smaller ``max_dets`` entries are honoured.  ``keep_similarity``: also download the similarity matrices (``similarity``);
+    the stats do not need them."""
+
+    def __init__(self, packed_gt, packed_dt, iou_type, device=None, keep_similarity=False):
+        self.keep_similarity = keep_similarity
+        self.params = EvalParams(iou_type)
+        if len(packed_dt.score) and packed_dt.kind != iou_type:
+            raise ValueError('the detections were packed as %r results (sorted and cut for that type), not %r'
+                             % (packed_dt.kind, iou_type))
+        self.gt, self.dt = packed_gt, packed_dt
+        self.params.img_ids, self.params.cat_ids = list(packed_gt.img_ids), list(packed_gt.cat_ids)
+        self.device = _default_device() if device is None else device
+        self.eval_imgs, self.eval, self.stats = None, {}, None
+        self._out = None
+
+    # --- evaluate ---------------------------------------------------------------------------------
+    def _chunks(self, limit):
+        """the cell table (cells with a detection or a ground truth), cut where a chunk would pass ``limit`` detections.
+        Detections and ground truths are both in cell order, so a run of cells owns one slice of each."""
+        p, g, d = self.params, self.gt, self.dt
+        kp = p.iou_type == 'keypoints'
+        dn, gn = np.diff(d.start), np.diff(g.start)
+        live = np.nonzero((dn > 0) | (gn > 0))[0]
+        cells = np.stack([d.start[live], dn[live], g.start[live], gn[live]], axis=1)
+        base = ((g.iscrowd != 0) | (g.num_keypoints == 0)) if kp else (g.iscrowd != 0)
+        common = dict(iou_type=p.iou_type, var=(landmark_meta()['oks_sigmas'] * 2) ** 2,
+                      area_rng=np.asarray(p.area_rng, dtype=np.float64).reshape(-1, 2),
+                      best0=np.minimum(np.asarray(p.iou_thrs, dtype=np.float64), 1 - 1e-10))
+        lo = 0
+        while lo < len(cells):
+            hi = int(np.searchsorted(cells[:, 0] + cells[:, 1], cells[lo, 0] + limit, side='right'))
+            hi = max(hi, lo + 1)
+            d0, d1 = int(cells[lo, 0]), int(cells[hi - 1, 0] + cells[hi - 1, 1])
+            g0, g1 = int(cells[lo, 2]), int(cells[hi - 1, 2] + cells[hi - 1, 3])
+            local = cells[lo:hi] - np.array([d0, 0, g0, 0])
+            size = local[:, 1] * local[:, 3]
+            yield Packed(d0=d0, d1=d1, g0=g0, g1=g1, nd=d1 - d0, ng=g1 - g0, cells=local,
+                         sim_off=np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64), sim_size=int(size.sum()),
+                         d_box=d.bbox[d0:d1], d_area=d.area[d0:d1], d_kxy=(d.kxy[d0:d1] if d.kxy is not None else np.zeros((0, g.num_landmarks, 2))) if kp else None,
+                         g_box=g.bbox[g0:g1], g_area=g.area[g0:g1], g_kpt=g.keypoints[g0:g1] if kp else None,
+                         g_crowd=g.iscrowd[g0:g1], g_nvis=g.num_visible[g0:g1], g_ign=base[g0:g1].astype(np.uint8), **common)
+            lo = hi
+
+    def evaluate(self):
+        p = self.params
+        if not p.use_cats:
+            raise ValueError('use_cats = 0 is not offered on the packed path: use evaluation.CocoEvaluator')
+        if p.iou_type == 'keypoints' and len(self.dt.score) and self.dt.kxy is None:
+            raise ValueError('landmark evaluation needs landmark detections')
+        if (not np.array_equal(np.unique(p.img_ids), self.gt.img_ids) or not np.array_equal(np.unique(p.cat_ids), self.gt.cat_ids)):
+            raise ValueError('params.img_ids / cat_ids differ from the packed ground truth: the cells are fixed by packing '
+                             '(pack the subset, or use evaluation.CocoEvaluator)')
+        p.max_dets = sorted(p.max_dets)
+        if p.max_dets[-1] != MAX_DETS[p.iou_type]:
+            raise ValueError('params.max_dets[-1] = %r, but the detections were cut to %d per cell when they were packed'
+                             % (p.max_dets[-1], MAX_DETS[p.iou_type]))
+        A, T = len(p.area_rng), len(p.iou_thrs)
+        nd, ng = len(self.dt.score), len(self.gt.id)
+        d_match = d_ignore = g_ignore = None
+        sims = []
+        run = _run_host if str(self.device) == 'cpu' else (lambda c, want: _run_device(c, self.device, want))
+        for c in self._chunks(CHUNK_DETS[p.iou_type]):
+            sim, dm, di, gi = run(c, self.keep_similarity)
+            if c.g0:
+                np.add(dm, c.g0, out=dm, where=dm > 0)             # chunk-local -> packed index, in place
+            if c.nd == nd and c.ng == ng:
+                d_match, d_ignore, g_ignore = dm, di, gi            # one chunk: the downloaded arrays as they are
+            else:
+                if d_match is None:
+                    d_match, d_ignore = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8)
+                    g_ignore = np.zeros((ng, A), np.uint8)
+                d_match[c.d0:c.d1], d_ignore[c.d0:c.d1], g_ignore[c.g0:c.g1] = dm, di, gi
+            sims.append(sim)
+        if d_match is None:
+            d_match, d_ignore, g_ignore = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8), np.zeros((ng, A), np.uint8)
+        size = np.diff(self.dt.start) * np.diff(self.gt.start)
+        self._out = Packed(d_match=d_match, d_ignore=d_ignore.view(bool), g_ignore=g_ignore,
+                           sim=(np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None,
+                           sim_start=np.concatenate([[0], np.cumsum(size)]).astype(np.int64))
+        return self
+
+    # --- accessors at the level of CocoEvaluator's intermediate results -----------------------------
+    def _cell(self, img_id, cat_id):
+        (i,), (oki,) = _index_of(self.gt.img_ids, [img_id])
+        (k,), (okk,) = _index_of(self.gt.cat_ids, [cat_id])
+        if not (oki and okk):
+            raise KeyError((img_id, cat_id))
+        return int(i) * len(self.gt.cat_ids) + int(k)
+
+    def similarity(self, img_id, cat_id):
+        """the [D, G] matrix of one (image, category), rows in descending-score order; [0, 0] when either side is empty"""
+        c = self._cell(img_id, cat_id)
+        D, G = int(self.dt.start[c + 1] - self.dt.start[c]), int(self.gt.start[c + 1] - self.gt.start[c])
+        if D == 0 or G == 0:
+            return np.zeros((0, 0))
+        if self._out.sim is None:
+            raise RuntimeError('the similarities were not downloaded: construct with keep_similarity=True')
+        s = self._out.sim_start[c]
+        return self._out.sim[s:s + D * G].reshape(D, G).copy()
+
+    def eval_imgs_of(self, k, a, i):
+        """what ``CocoEvaluator.eval_imgs[(k * A + a) * I + i]`` holds: None, or d_match [T, D] (ground-truth ids, 0 = none),
+        d_scores [D], g_ignore [G] (regular first, as the reference orders the ground truths), d_ignore [T, D]"""
+        c = i * len(self.gt.cat_ids) + k
+        d0, d1, g0, g1 = self.dt.start[c], self.dt.start[c + 1], self.gt.start[c], self.gt.start[c + 1]
+        if d0 == d1 and g0 == g1:
+            return None
+        m = self._out.d_match[d0:d1, a, :].T
+        ids = self.gt.id[np.maximum(m, 1) - 1] if len(self.gt.id) else np.zeros(m.shape, np.int64)
+        return dict(d_match=np.where(m > 0, ids, 0).astype(np.float64), d_scores=self.dt.score[d0:d1].copy(),
+                    g_ignore=np.sort(self._out.g_ignore[g0:g1, a].astype(np.int64)),
+                    d_ignore=self._out.d_ignore[d0:d1, a, :].T.copy())
+
+    # --- accumulate ---------------------------------------------------------------------------------
+    def accumulate(self):
+        """``CocoEvaluator.accumulate`` on the packed outputs: per (category, area range, max_dets) one stable score sort, integer
+        cumulative sums over all thresholds at once, the precision envelope and ``searchsorted(side='left')`` per threshold."""
+        if self._out is None:
+            raise RuntimeError('Please run evaluate() first')
+        p, d, g, o = self.params, self.dt, self.gt, self._out
+        T, R, K, A, M = len(p.iou_thrs), len(p.rec_thrs), len(p.cat_ids), len(p.area_rng), len(p.max_dets)
+        precision, recall, scores = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M)), -np.ones((T, R, K, A, M))
+        eps = np.spacing(1)
+        rec_thrs = np.asarray(p.rec_thrs)
+        rank = np.arange(len(d.score)) - d.start[d.cell] if len(d.score) else np.zeros(0, np.int64)
+        d_by_cat = np.argsort(d.cat_idx, kind='mergesort')          # (inside a category: image order, then rank)
+        d_cut = np.searchsorted(d.cat_idx[d_by_cat], np.arange(K + 1))
+        g_by_cat = np.argsort(g.cat_idx, kind='mergesort')
+        g_cut = np.searchsorted(g.cat_idx[g_by_cat], np.arange(K + 1))
+        for k in range(K):
+            dk, gk = d_by_cat[d_cut[k]:d_cut[k + 1]], g_by_cat[g_cut[k]:g_cut[k + 1]]
+            rank_k, score_k = rank[dk], d.score[dk]
+            matched_k, ignored_k = o.d_match[dk] != 0, o.d_ignore[dk]          # [n, A, T], gathered once per category
+            for a in range(A):
+                n_gt = int(np.count_nonzero(o.g_ignore[gk, a] == 0))
+                if n_gt == 0:
+                    continue
+                for m, max_det in enumerate(p.max_dets):
+                    sel = np.nonzero(rank_k < max_det)[0]
+                    sc = score_k[sel]
+                    order = np.argsort(-sc, kind='mergesort')
+                    sc, sel = sc[order], sel[order]
+                    matched = np.ascontiguousarray(matched_k[sel, a, :].T)
+                    ignored = np.ascontiguousarray(ignored_k[sel, a, :].T)
+                    tp = np.cumsum(matched & ~ignored, axis=1).astype(np.float64)
+                    fp = np.cumsum(~matched & ~ignored, axis=1).astype(np.float64)
+                    rc = tp / n_gt
+                    pr = tp / (fp + tp + eps)
+                    recall[:, k, a, m] = rc[:, -1] if len(sel) else 0
+                    pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]
+                    for t in range(T):
+                        pos = np.searchsorted(rc[t], rec_thrs, side='left')
+                        ok = pos < len(sel)
+                        q, s = np.zeros(R), np.zeros(R)
+                        q[ok], s[ok] = pr[t, pos[ok]], sc[pos[ok]]
+                        precision[t, :, k, a, m], scores[t, :, k, a, m] = q, s
+        self.eval = dict(counts=[T, R, K, A, M], precision=precision, recall=recall, scores=scores)
+        return self
+
+
+def evaluate_packed(packed_gt, packed_dt, iou_type, device=None, verbose=False):
+    return DeviceCocoEvaluator(packed_gt, packed_dt, iou_type, device).evaluate().accumulate().summarize(verbose)
+
+
+def evaluate_results(dataset, results, result_types=('bbox', 'keypoints'), device=None, packed_gt=None, verbose=False):
+    """{type: stats} for what ``single_gpu_test`` / ``multi_gpu_test`` returned for ``dataset``, without result files: the
+    numbers of ``coco_eval(results2json(dataset, results, ...), result_types, dataset.coco)``.  ``packed_gt``: the dataset's
+    ``pack_ground_truth(dataset.coco)`` when the caller keeps it between calls (a validation hook does)."""
+    for t in result_types:
+        if t not in ('bbox', 'keypoints'):
+            raise ValueError('unsupported result type {!r}'.format(t))
+    if packed_gt is None:
+        packed_gt = pack_ground_truth(dataset.coco)
+    packed = pack_test_results(packed_gt, dataset, results)
+    out = {}
+    for t in result_types:
+        if t not in packed:
+            raise ValueError('the results hold no {!r} detections'.format(t))
+        out[t] = evaluate_packed(packed_gt, packed[t], t, device, verbose)
+    return out

@@ -385,8 +385,12 @@ class GraphedTrainStep(object):
 
 class Runner(object):
     def __init__(self, model, optimizer, work_dir=None, lr_config=None, optimizer_config=None, checkpoint_config=None,
-                 log_interval=50, logger=print, batch_processor=batch_processor):
+                 log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None):
+        """``eval_config = dict(dataset=..., interval=1, imgs_per_gpu=1, device_preprocess=False, group=None, to_device=None,
+        result_types=('bbox', 'keypoints'), device=None)``: validation after every ``interval``-th epoch (``validate``)."""
         self.model, self.optimizer, self.work_dir = model, optimizer, work_dir
+        self.eval_config = dict(eval_config) if eval_config else None
+        self._packed_gt = None
         self.lr = LrSchedule(**(lr_config or dict(policy='step', step=[])))
         self.opt_hook = DistOptimizerHook(**(optimizer_config or {}))
         self.ckpt_interval = (checkpoint_config or {}).get('interval', 1)
@@ -443,4 +447,51 @@ class Runner(object):
             self.train_epoch(data_loader, to_device)
             if self.work_dir is not None and self.ckpt_interval > 0 and self.epoch % self.ckpt_interval == 0:
                 self.save_checkpoint()
+            if self.eval_config is not None and self.epoch % self.eval_config.get('interval', 1) == 0:
+                self.validate()
         return self
+
+    def validate(self):
+        """The reference's ``CocoDistEvalmAPHook`` (mmdet/core/evaluation/eval_hooks.py:136-172) after a training epoch: the
+        model in ``eval()``, ``single_gpu_test`` -- ``multi_gpu_test`` when ``eval_config['group']`` is given -- over the
+        validation dataset, the results evaluated on rank 0 without result files (``evaluation_device.evaluate_results``, on
+        the GPU unless ``eval_config['device']`` says otherwise), one record appended to ``log_history`` and logged, the model
+        back in ``train()`` (which drops the inference-time weight caches).  The ground truth is packed once and kept.
+        Record: ``epoch`` and, per result type, ``{type}_mAP``, ``_mAP_50``, ``_mAP_75``, ``_mAP_s``, ``_mAP_m``, ``_mAP_l`` =
+        ``float('%.3f' % stats[i])`` for i = 0..5 plus ``{type}_mAP_copypaste``.  As in the reference the six names are applied
+        to ``stats[0..5]`` of EITHER type: for 'keypoints' ``stats[3..5]`` are AP-medium, AP-large and AR, not small / medium /
+        large.  Callers of ``GraphedTrainStep`` run ``refresh_inference_caches()`` and then this method between replays.
+        Returns the record (None on the other ranks)."""
+        from . import evaluation_device as evd
+        cfg = self.eval_config
+        dataset, group = cfg['dataset'], cfg.get('group')
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            kw = dict(rescale=True, to_device=cfg.get('to_device'), imgs_per_gpu=cfg.get('imgs_per_gpu', 1),
+                      device_preprocess=cfg.get('device_preprocess', False))
+            if group is not None:
+                results = multi_gpu_test(self.model, dataset, group=group, **kw)
+            else:
+                results = single_gpu_test(self.model, dataset, **kw)
+        finally:
+            self.model.train(was_training)
+        if results is None:                     # (not rank 0)
+            return None
+        if self._packed_gt is None:
+            self._packed_gt = evd.pack_ground_truth(dataset.coco)
+        device = cfg.get('device')
+        if device is None:
+            device = next(self.model.parameters()).device
+        types = [t for t in cfg.get('result_types', ('bbox', 'keypoints'))
+                 if t == 'bbox' or isinstance(results[0], tuple)]
+        stats = evd.evaluate_results(dataset, results, types, device=device, packed_gt=self._packed_gt)
+        rec = OrderedDict(epoch=self.epoch)
+        for t in types:
+            names = ['mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l']
+            for i, name in enumerate(names):
+                rec['{}_{}'.format(t, name)] = float('{:.3f}'.format(stats[t][i]))
+            rec['{}_mAP_copypaste'.format(t)] = ('{:.3f} ' * 6).format(*stats[t][:6]).strip()
+        self.log_history.append(rec)
+        self.logger(', '.join('%s: %s' % kv for kv in rec.items()))
+        return rec

@@ -1,0 +1,235 @@
+"""kgdet_amd.evaluation_device without a GPU: packing, ordering, the numpy restatement of the two kernels and the vectorised
+accumulate against evaluation.CocoEvaluator -- EQUAL at every level -- and against the reference evaluator's golden arrays."""
+import copy
+import json
+
+import numpy as np
+import pytest
+
+from kgdet_amd import evaluation as ev
+from kgdet_amd import evaluation_device as evd
+from tests import eval_cases as cases
+
+TYPES = ['bbox', 'keypoints']
+
+
+@pytest.mark.parametrize('case', ['a', 'b', 'gt', 'live'])
+@pytest.mark.parametrize('typ', TYPES)
+def test_restatement_equals_coco_evaluator_on_the_golden_cases(case, typ):
+    gt, results = cases.golden_case(case)
+    want = cases.host_evaluator(gt, results[typ], typ)
+    got = cases.packed_evaluator(gt, results[typ], typ, 'cpu')
+    stats, prec, rec = cases.golden_arrays(case, typ)
+    np.testing.assert_allclose(got.stats, stats, rtol=0, atol=1e-12)
+    if prec is not None:
+        np.testing.assert_allclose(got.eval['precision'], prec, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(got.eval['recall'], rec, rtol=0, atol=1e-12)
+    for i, c, mine, theirs in cases.similarities(got, want):
+        assert mine.shape == theirs.shape and np.array_equal(mine, theirs), (i, c)
+    cases.assert_same_matching(got, want)
+
+
+@pytest.mark.parametrize('typ', TYPES)
+def test_restatement_equals_coco_evaluator_on_the_stress_set(typ):
+    gt, results = cases.stress_case()
+    want = cases.host_evaluator(gt, results[typ], typ)
+    got = cases.packed_evaluator(gt, results[typ], typ, 'cpu')
+    # the set really holds what it is meant to hold
+    anns = gt['annotations']
+    assert any(a['iscrowd'] for a in anns) and any(a['num_keypoints'] == 0 for a in anns)
+    assert any(not any(v > 0 for v in a['keypoints'][2::3]) and a['num_keypoints'] > 0 for a in anns)
+    with_gt, with_dt = {a['image_id'] for a in anns}, {r['image_id'] for r in results[typ]}
+    all_imgs = {im['id'] for im in gt['images']}
+    assert all_imgs - with_gt and all_imgs - with_dt and (with_dt - with_gt) and (with_gt - with_dt)
+    cells = {}
+    for r in results[typ]:
+        cells.setdefault((r['image_id'], r['category_id']), []).append(r['score'])
+    assert max(len(v) for v in cells.values()) > 100
+    assert any(len(set(v)) < len(v) for v in cells.values())                    # equal scores inside a cell
+    assert {1024.0, 9216.0, 1023.999, 9216.001} <= {a['area'] for a in anns}
+    assert {1024.0, 9216.0} <= set(got.dt.area.tolist())
+    tied = sum(int((np.sort(s, axis=1)[:, 1:] == np.sort(s, axis=1)[:, :-1]).any()) for _, _, s, _ in cases.similarities(got, want)
+               if s.shape[1] > 1)
+    assert tied > 0                                                             # one detection, two equal candidates
+    assert 0.05 < want.stats[0] < 0.95
+    for i, c, mine, theirs in cases.similarities(got, want):
+        assert mine.shape == theirs.shape and np.array_equal(mine, theirs), (i, c)
+    cases.assert_same_matching(got, want)
+
+
+def test_chunked_evaluation_gives_the_same_arrays(monkeypatch):
+    gt, results = cases.stress_case()
+    whole = cases.packed_evaluator(gt, results['bbox'], 'bbox', 'cpu')
+    monkeypatch.setitem(evd.CHUNK_DETS, 'bbox', 37)
+    parts = cases.packed_evaluator(gt, results['bbox'], 'bbox', 'cpu')
+    assert len(list(parts._chunks(37))) > 5
+    for key in ('d_match', 'd_ignore', 'g_ignore', 'sim'):
+        assert np.array_equal(getattr(whole._out, key), getattr(parts._out, key)), key
+    assert np.array_equal(whole.stats, parts.stats)
+
+
+class _Dataset(object):
+    def __init__(self, img_ids, cat_ids, coco=None):
+        self.img_ids, self.cat_ids, self.coco = img_ids, cat_ids, coco
+
+    def __len__(self):
+        return len(self.img_ids)
+
+
+def _detector_results(gt, seed, awkward=True):
+    """detector-shaped float32 results for the demo images: per class boxes [n, 5] xyxy + score, scores, landmarks [n, 882]"""
+    rng = np.random.default_rng(seed)
+    n_cls = len(gt['categories'])
+    by_img = {}
+    for a in gt['annotations']:
+        by_img.setdefault(a['image_id'], []).append(a)
+    # A float32 widened to float64 has 29 zero bits at the end and never lands within a rounding error of a decimal half, so
+    # round(v, 4) == np.round(v, 4) for every coordinate and score by itself; the WIDTH x2 - x1 + 1 is a float64 sum and can.
+    # These float32 corner pairs give widths one ulp beside 0.99985 / 0.99975 / 0.99965: Python rounds the exact value,
+    # np.round multiplies by 1e4 first, lands on the half and rounds to even.
+    odd = [(0.0001500000071246177, 7.124634215927017e-12), (0.0002500000118743628, 1.18742793375759e-11),
+           (0.0003499999875202775, -1.2479683952903997e-11)]
+    for x1, x2 in odd:
+        assert float(np.float32(x1)) == x1 and float(np.float32(x2)) == x2
+        assert round(x2 - x1 + 1, 4) != np.round(x2 - x1 + 1, 4)
+    results = []
+    for im in gt['images']:
+        det = [np.zeros((0, 5), np.float32) for _ in range(n_cls)]
+        kpt = [np.zeros((0, 882), np.float32) for _ in range(n_cls)]
+        for a in by_img.get(im['id'], []):
+            lab = [c['id'] for c in gt['categories']].index(a['category_id'])
+            if rng.random() < 0.2:
+                lab = int(rng.integers(0, n_cls))
+            for _ in range(int(rng.integers(1, 4))):
+                x, y, w, h = np.asarray(a['bbox']) + rng.normal(0, 0.05, 4) * max(a['bbox'][2:])
+                row = np.array([[x, y, x + w, y + h, rng.random()]], np.float32)
+                k = (np.asarray(a['keypoints'], dtype=np.float64) + rng.normal(0, 2.0, 882)).astype(np.float32)[None]
+                if awkward:
+                    c = 2 * int(rng.integers(0, 2))                 # (x or y pair)
+                    row[0, c // 2], row[0, 2 + c // 2] = odd[int(rng.integers(0, len(odd)))]
+                det[lab] = np.concatenate([det[lab], row])
+                kpt[lab] = np.concatenate([kpt[lab], k])
+        results.append((det, [d[:, 4] for d in det], kpt))
+    return results
+
+
+def test_round_like_python_is_pythons_round():
+    rng = np.random.default_rng(3)
+    v = np.concatenate([rng.random(20000).astype(np.float32).astype(np.float64) * 10.0 ** rng.integers(-3, 4, 20000),
+                        (rng.integers(0, 10 ** 7, 20000) * 1e-4 + 0.5e-4),           # decimal ties as float64
+                        (rng.integers(0, 10 ** 7, 20000) * 1e-4 + 0.5e-4).astype(np.float32).astype(np.float64),
+                        np.array([0.0, -0.0, 2.675, 1e15, -1e15 + 0.3, 5e-5, -5e-5, 1.00005, 0.28515, 1e300, -3.00005])])
+    want = np.array([round(float(x), 4) for x in v])
+    assert np.array_equal(evd.round_like_python(v, 4), want)
+    assert (np.round(v, 4) != want).any()                  # (the shortcut without the repair would be wrong here)
+    assert np.array_equal(evd.round_like_python(v[:100], 0), np.array([round(float(x), 0) for x in v[:100]]))
+
+
+def test_pack_test_results_equals_the_route_through_files(tmp_path):
+    gt = cases.demo_gt()
+    index = ev.CocoIndex(copy.deepcopy(gt))
+    data = _Dataset(index.get_img_ids(), index.get_cat_ids(), index)
+    results = _detector_results(gt, seed=11)
+    # the inputs hold values where the two roundings differ
+    rows = np.concatenate([d.astype(np.float64) for r in results for d in r[0]])
+    flat = np.concatenate([rows[:, 2] - rows[:, 0] + 1, rows[:, 3] - rows[:, 1] + 1])
+    assert (np.round(flat, 4) != np.array([round(float(x), 4) for x in flat])).sum() > 20
+    files = ev.results2json(data, results, str(tmp_path / 'res'))
+    pg = evd.pack_ground_truth(index)
+    packed = evd.pack_test_results(pg, data, results)
+    for typ in TYPES:
+        via_files = evd.pack_results(pg, files[typ])
+        loaded = index.load_results(files[typ]).dataset['annotations']
+        assert len(loaded) > 50
+        for key in ('cell', 'start', 'score', 'bbox', 'area', 'id', 'img_idx', 'cat_idx'):
+            assert np.array_equal(getattr(packed[typ], key), getattr(via_files, key)), (typ, key)
+        by_id = {r['id']: r for r in loaded}
+        for n, i in enumerate(packed[typ].id):             # and against load_results itself, value for value
+            r = by_id[int(i)]
+            assert list(packed[typ].bbox[n]) == [float(v) for v in r['bbox']] and packed[typ].area[n] == r['area']
+            assert packed[typ].score[n] == r['score']
+            assert pg.img_ids[packed[typ].img_idx[n]] == r['image_id'] and pg.cat_ids[packed[typ].cat_idx[n]] == r['category_id']
+            if typ == 'keypoints':
+                k = np.asarray(r['keypoints']).reshape(-1, 3)[:, :2]
+                assert np.array_equal(packed[typ].kxy[n], k)
+        assert np.array_equal(packed['keypoints'].kxy, evd.pack_results(pg, files['keypoints']).kxy)
+    # end to end: evaluate_results == coco_eval over the files, on both routes of coco_eval
+    want = ev.coco_eval(files, TYPES, index, verbose=False)
+    got = evd.evaluate_results(data, results, TYPES, device='cpu')
+    routed = ev.coco_eval(files, TYPES, index, verbose=False, device='cpu')
+    for typ in TYPES:
+        assert np.array_equal(got[typ], want[typ]) and np.array_equal(routed[typ], want[typ])
+    # plain per-class box lists take det2json's route (no rounding)
+    plain = [r[0] for r in results]
+    files = ev.results2json(data, plain, str(tmp_path / 'plain'))
+    a, b = evd.pack_test_results(pg, data, plain)['bbox'], evd.pack_results(pg, files['bbox'])
+    for key in ('cell', 'score', 'bbox', 'area', 'id'):
+        assert np.array_equal(getattr(a, key), getattr(b, key)), key
+
+
+def test_error_paths():
+    gt, results = cases.golden_case('a')
+    index = ev.CocoIndex(gt)
+    pg = evd.pack_ground_truth(index)
+    bad = copy.deepcopy(results['bbox'][:3])
+    bad[1]['image_id'] = 10 ** 9
+    with pytest.raises(ValueError, match='do not correspond'):
+        evd.pack_results(pg, bad)
+    with pytest.raises(ValueError, match='only bbox and keypoints'):
+        evd.pack_results(pg, [dict(image_id=results['bbox'][0]['image_id'], category_id=1, score=0.5, segmentation=[])])
+    with pytest.raises(TypeError):
+        evd.pack_results(pg, dict(a=1))
+    data = _Dataset([10 ** 9], index.get_cat_ids(), index)
+    one = np.array([[1, 2, 30, 40, 0.5]], np.float32)
+    empty = np.zeros((0, 5), np.float32)
+    res = [([one] + [empty] * 12, None, [np.zeros((1, 882), np.float32)] + [np.zeros((0, 882), np.float32)] * 12)]
+    with pytest.raises(ValueError, match='do not correspond'):
+        evd.pack_test_results(pg, data, res)
+    with pytest.raises(TypeError):
+        evd.pack_test_results(pg, data, [np.zeros((1, 5))])
+    packed = evd.pack_results(pg, copy.deepcopy(results['bbox']))
+    e = evd.DeviceCocoEvaluator(pg, packed, 'bbox', device='cpu')
+    e.params.use_cats = 0
+    with pytest.raises(ValueError, match='CocoEvaluator'):
+        e.evaluate()
+    for edit in (lambda q: setattr(q, 'img_ids', q.img_ids[:5]), lambda q: setattr(q, 'cat_ids', q.cat_ids[:3]),
+                 lambda q: setattr(q, 'max_dets', [1, 10, 50])):
+        e = evd.DeviceCocoEvaluator(pg, packed, 'bbox', device='cpu')
+        edit(e.params)
+        with pytest.raises(ValueError, match='pack'):
+            e.evaluate()
+    e = evd.DeviceCocoEvaluator(pg, packed, 'bbox', device='cpu')
+    e.params.max_dets = [100, 5]                            # the smaller entries are honoured, in sorted order as CocoEvaluator sorts them
+    h = ev.CocoEvaluator(index, index.load_results(copy.deepcopy(results['bbox'])), 'bbox')
+    h.params.max_dets = [100, 5]
+    assert np.array_equal(e.evaluate().accumulate().eval['precision'], h.evaluate().accumulate().eval['precision'])
+    with pytest.raises(RuntimeError, match='keep_similarity'):
+        e.similarity(pg.img_ids[0], pg.cat_ids[0])
+    zero = copy.deepcopy(gt)
+    zero['annotations'][0]['id'] = 0
+    with pytest.raises(ValueError, match='id 0'):
+        evd.pack_ground_truth(ev.CocoIndex(zero))
+    with pytest.raises(ValueError, match='packed as'):
+        evd.DeviceCocoEvaluator(pg, packed, 'keypoints', device='cpu')
+    with pytest.raises(ValueError):
+        evd.DeviceCocoEvaluator(pg, packed, 'segm', device='cpu')
+    with pytest.raises(RuntimeError):
+        evd.DeviceCocoEvaluator(pg, packed, 'bbox', device='cpu').accumulate()
+    with pytest.raises(ValueError, match='unsupported result type'):
+        evd.evaluate_results(data, res, ['segm'], device='cpu')
+    # no detections at all: CocoEvaluator's answer (every recall 0 where there is ground truth)
+    none = evd.DeviceCocoEvaluator(pg, evd.pack_results(pg, []), 'keypoints', device='cpu').evaluate().accumulate()
+    want = cases.host_evaluator(gt, [], 'keypoints')
+    assert np.array_equal(none.summarize(verbose=False), want.stats)
+    # an unknown category is dropped, as CocoEvaluator never loads it
+    odd = copy.deepcopy(results['bbox'])
+    odd[0]['category_id'] = 999
+    cases.assert_same_matching(cases.packed_evaluator(gt, odd, 'bbox', 'cpu'), cases.host_evaluator(gt, odd, 'bbox'))
+
+
+def test_runner_without_eval_config_has_no_hook():
+    from kgdet_amd import runner as rn
+    import inspect
+    assert inspect.signature(rn.Runner.__init__).parameters['eval_config'].default is None
+    assert json.dumps(evd.MAX_DETS, sort_keys=True) == json.dumps(
+        {t: ev.EvalParams(t).max_dets[-1] for t in TYPES}, sort_keys=True)
