@@ -481,6 +481,10 @@ int kgdet_pts_from_offsets_backward(const float *grad_pts, float *grad_pred, int
  * are scaled by min(1, max_norm / (norm[0] + 1e-6)) in place (max_norm <= 0: no clipping), then the Adam update with
  * bias_correction1 = 1 - beta1^step and bias_correction2_sqrt = sqrt(1 - beta2^step) of the step being taken; weight decay
  * is added to the gradient (Adam, not AdamW); the betas come as doubles so that 1 - beta is rounded once, as torch does.  No amsgrad / maximize.  Deterministic; no host synchronisation.
+ * Non-finite gradients behave as in torch: a NaN gradient makes norm[0] and the coefficient NaN, and every gradient, moment and
+ * parameter of the table becomes NaN (clip_grad_norm_ multiplies by the clamped coefficient, and clamp keeps NaN) -- a poisoned
+ * step is loud instead of updating the finite-gradient parameters unclipped; an infinite gradient makes the coefficient 0: that
+ * element becomes NaN (inf * 0), every other gradient 0, and the step is taken from the moments alone.
  */
 int32_t kgdet_optim_chunk(void);
 int kgdet_multi_grad_norm(const int64_t *table_dev, int32_t n, int64_t total_blocks, float *partial, float *norm_out, void *stream);

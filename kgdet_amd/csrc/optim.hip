@@ -103,9 +103,9 @@ __global__ __launch_bounds__(256) void multi_clip_adam(const long long *__restri
   float coef = 1.0f;
   if (max_norm > 0.0f) {
     coef = max_norm / (norm[0] + 1e-6f);     // clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
-    coef = coef < 1.0f ? coef : 1.0f;
+    coef = coef >= 1.0f ? 1.0f : coef;       // (a NaN norm stays a NaN coefficient, as torch.clamp leaves it)
   }
-  const bool scale = coef < 1.0f;
+  const bool scale = !(coef >= 1.0f);        // NaN scales too: every gradient, and with it every parameter, turns NaN as in torch
   const float step_size = lr / bias_correction1, w1 = one_minus_beta1;   // (1 - beta rounded from double, as torch passes them)
   for (int k = 0; k < 16; ++k) {
     const long long i = base + k * 256 + threadIdx.x;
