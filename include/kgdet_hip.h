@@ -697,7 +697,9 @@ int kgdet_soft_nms(const float *dets, int64_t n, float iou_thr, int32_t method, 
 int kgdet_moment_bbox_forward(const float *pts, const float *moment_transfer, int32_t B, int32_t n_pts,
                               int32_t HW, int32_t y_first, float *bbox, void *stream);
 /* backward: grad_pts and grad_transfer [2] are OVERWRITTEN; the two transfer sums leave the blocks as partials in the
- * caller's workspace and are added in block order (no float atomics: bit-repeatable). */
+ * caller's workspace and are added in block order (no float atomics: bit-repeatable).  Where all points of a location
+ * coincide (std == 0) the box is the mean and grad_pts is the mean term (g_lo + g_hi) / n alone -- finite, what
+ * torch.std's backward fills in for 0 / 0 (tests/test_gpu_pointwise_kernels.py). */
 size_t kgdet_moment_bbox_backward_workspace_bytes(int32_t B, int32_t HW);
 int kgdet_moment_bbox_backward(const float *pts, const float *moment_transfer, const float *grad_bbox,
                                int32_t B, int32_t n_pts, int32_t HW, int32_t y_first, float *grad_pts,
