@@ -414,6 +414,11 @@ int kgdet_sigmoid_focal_loss_backward(const float *logits, const int64_t *target
  * (x = column * stride, y = row * stride).  losses[9] = cls 1-3, bbox 1-3, kpt 1-3; num_total = sum over images of
  * max(positives, 1) (a device scalar; nothing is read by the host).  The backward call takes the forward call's
  * workspace (it holds the per-gt selections) and writes every element of the nine gradient maps.
+ * Workspace layout: the first B * 64 * H * W floats are the selections dsel[b][g][i] -- row stride 64 whatever num_gt[b] is --
+ * = the distance of point i to ground truth g where i is among its pos_num nearest (ties: the lowest point index), +inf
+ * elsewhere; rows g >= num_gt[b] are not written.  A point goes to the selecting ground truth with the smallest value, the
+ * earliest on equal values.  Per-workgroup partial sums follow.  A workspace shorter than kgdet_head_loss_workspace_bytes():
+ * KGDET_E_WORKSPACE from either call.
  * Limits: B <= 16, 1..64 ground truths per image, H * W <= 4096.
  * ------------------------------------------------------------------------------------------ */
 #define KGDET_HEAD_MAX_IMAGES 16

@@ -83,7 +83,8 @@ __device__ __forceinline__ int final_assign(const float *__restrict__ dsel, int 
 
 }  // namespace
 
-// block (g, b), 256 threads.  dsel[b][g][i] = distance if point i is among the pos_num nearest of gt g, else +inf.
+// block (g, b), 256 threads.  dsel[b][g][i] = distance if point i is among the pos_num nearest of gt g, else +inf; row stride 64
+// (kMaxGt) whatever the images' gt counts, rows g >= num_gt[b] are left unwritten and never read.
 // "Among the pos_num nearest" = rank < pos_num under the (distance, point index) order.  Ranks are only needed for the
 // points within T = the largest distance inside a ceil(sqrt(pos_num))-sided block of grid points around the centre: that
 // block holds >= pos_num points, so every point beyond T has rank >= pos_num, and every point that precedes a candidate
@@ -401,8 +402,11 @@ int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_
   for (int s = 0; s < 3; ++s)
     KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s] && grads->cls[s] && grads->bbox[s] && grads->kpt[s],
                       "null map");
-  KGDET_CHECK_SHAPE(workspace && workspace_bytes >= kgdet_head_loss_workspace_bytes(t),
-                    "the forward call's workspace (the per-gt selections) is needed");
+  const size_t need = kgdet_head_loss_workspace_bytes(t);
+  if (workspace == nullptr || workspace_bytes < need) {
+    set_error("head_loss: the forward call's workspace (the per-gt selections, %zu bytes) is needed, got %zu", need, workspace_bytes);
+    return KGDET_E_WORKSPACE;
+  }
   const int N = t->H * t->W;
   const float *dsel = reinterpret_cast<const float *>(workspace);
   int groups = 0;
