@@ -506,6 +506,27 @@ int kgdet_multi_clip_adam(const int64_t *table_dev, int32_t n, int64_t total_blo
 int kgdet_multi_clip_adam_dev(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm, float max_norm,
                               float *sched, const float *lr_ring /*nullable*/, int32_t ring, double beta1, double beta2, float eps,
                               float weight_decay, void *stream);
+/*
+ * Gradient clipping + momentum SGD over the same table: clip_grad_norm_(params, max_norm, 2) followed by torch.optim.SGD.step()
+ * (torch/optim/sgd.py _single_tensor_sgd; the optimizer of the three DeepFashion2 configs: lr 5e-3, momentum 0.9, weight decay 1e-4).
+ * Row: {param, grad, momentum_buffer, ignored, numel, first block} -- slot 2 may be 0 only when momentum == 0 (the buffer is then
+ * neither read nor written; with momentum != 0 a row whose slot 2 is 0 is a table error: the caller that builds the table refuses
+ * it, and the kernel leaves such a row untouched rather than read through the pointer); slot 3 is never dereferenced.  Rows and
+ * blocks as above, so kgdet_multi_grad_norm serves both.  One pass, fp32, no atomics, deterministic:
+ *   g' = g min(1, max_norm / (norm[0] + 1e-6)) (written back only when the coefficient is below 1 or NaN; max_norm <= 0: no clipping,
+ *   norm may be NULL), d = g' + p weight_decay, buf = momentum buf + (1 - dampening) d, d = nesterov ? d + momentum buf : buf,
+ *   p -= lr d.  momentum and dampening come as doubles so that momentum and 1 - dampening are rounded once.  Non-finite gradients
+ * behave as described for Adam.  The first step of a torch optimizer (buf = d, no dampening) is not this kernel's: it needs the
+ * buffers to exist.
+ * kgdet_multi_clip_sgd_dev: the capturable form.  sched[4] as for Adam, of which SGD uses [0] = learning rate and [3] = steps
+ * taken: the call advances sched[3] to t, loads sched[0] = lr_ring[t % ring] when lr_ring != NULL (page-locked host memory read in
+ * place), then applies the update with sched[0].
+ */
+int kgdet_multi_clip_sgd(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm /*nullable*/, float max_norm,
+                         float lr, double momentum, double dampening, float weight_decay, int32_t nesterov, void *stream);
+int kgdet_multi_clip_sgd_dev(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm /*nullable*/,
+                             float max_norm, float *sched, const float *lr_ring /*nullable*/, int32_t ring, double momentum,
+                             double dampening, float weight_decay, int32_t nesterov, void *stream);
 
 /*
  * GroupNorm (+ ReLU) of the ConvModules of the head towers and the neck as one pass each way -- ATen runs it as ten kernels

@@ -1,15 +1,20 @@
-// Gradient clipping + Adam of the training step as multi-tensor passes (gfx950).
+// Gradient clipping + the optimizer update of the training step as multi-tensor passes (gfx950).
 //
 // The reference's step is OptimizerHook.after_train_iter: clip_grad_norm_ (max_norm 35, L2) then optimizer.step()
-// (mmdet/core/utils/dist_utils.py:44-58 -> mmcv OptimizerHook; the KGDet config trains with Adam).  torch runs that as
-// three multi-tensor norm launches + a reduction, a chain of scalar ops, three multi-tensor scale launches and six fused-Adam
-// launches over the ~50 M parameters: 0.57 ms of a 15 ms step, at about half the memory bandwidth.  Here:
+// (mmdet/core/utils/dist_utils.py:44-58 -> mmcv OptimizerHook).  The 32-image demo config trains with Adam; the three
+// DeepFashion2 configs (kgdet_moment_r50_fpn_1x, the two reppoints_moment_*) with SGD(lr 5e-3, momentum 0.9, weight decay 1e-4).
+// torch runs the Adam step as three multi-tensor norm launches + a reduction, a chain of scalar ops, three multi-tensor scale
+// launches and six fused-Adam launches over the ~50 M parameters: 0.57 ms of a 15 ms step, at about half the memory bandwidth;
+// the SGD step is the same chain in front of the foreach SGD launches.  Here:
 //   multi_sqnorm    one pass over all gradients -> per-block partial sums -> ||g||^2 (fixed order: deterministic)
 //   multi_clip_adam one pass: coef = min(1, max_norm / (||g|| + 1e-6)) read from the device scalar (no host round trip),
 //                   g' = coef g (written back only when coef < 1: clip_grad_norm_ scales the gradients in place),
 //                   then torch's Adam update expression by expression (torch/optim/adam.py _single_tensor_adam /
 //                   fused_adam_utils.cuh adam_math, ADAM mode ORIGINAL: weight decay added to the gradient).
-// Table row per tensor: {param, grad, exp_avg, exp_avg_sq, numel, first block}; a block covers kOptChunk elements.
+//   multi_clip_sgd  the same clip, then torch/optim/sgd.py _single_tensor_sgd expression by expression: weight decay added to
+//                   the gradient, buf = momentum buf + (1 - dampening) d, Nesterov or plain, p -= lr d.
+// Table row per tensor: {param, grad, exp_avg, exp_avg_sq, numel, first block} (SGD: {param, grad, momentum_buffer or 0,
+// ignored, numel, first block}); a block covers kOptChunk elements.
 #include "common.h"
 
 namespace kgdet {
@@ -128,6 +133,111 @@ __global__ __launch_bounds__(256) void multi_clip_adam(const long long *__restri
   }
 }
 
+// SGD under the device schedule: sched[3] = t advances by one, sched[0] = this step's learning rate from slot t % ring of the
+// page-locked ring (read in place, as adam_schedule_step reads it); sched[1], sched[2] are not used.
+__global__ void sgd_schedule_step(float *__restrict__ sched, const float *__restrict__ lr_ring, int ring) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float t = sched[3] + 1.0f;
+  sched[3] = t;
+  if (lr_ring) sched[0] = lr_ring[(long long)t % ring];
+}
+
+namespace {
+struct SgdArgs {
+  float coef, lr, momentum, one_minus_dampening, weight_decay;
+  bool scale, nesterov;
+};
+
+// torch/optim/sgd.py _single_tensor_sgd for one element: gv the (clipped) gradient, bv the momentum buffer (untouched when
+// momentum == 0), pv the parameter
+__device__ __forceinline__ void sgd_element(const SgdArgs &a, float &pv, float &gv, float &bv) {
+  if (a.scale) gv *= a.coef;
+  float d = gv;
+  if (a.weight_decay != 0.0f) d += pv * a.weight_decay;
+  if (a.momentum != 0.0f) {
+    bv = a.momentum * bv + a.one_minus_dampening * d;
+    d = a.nesterov ? d + a.momentum * bv : bv;
+  }
+  pv -= a.lr * d;
+}
+
+__device__ __forceinline__ void sgd_quad(const SgdArgs &a, float4 &pv, float4 &gv, float4 &bv) {
+  sgd_element(a, pv.x, gv.x, bv.x);
+  sgd_element(a, pv.y, gv.y, bv.y);
+  sgd_element(a, pv.z, gv.z, bv.z);
+  sgd_element(a, pv.w, gv.w, bv.w);
+}
+}  // namespace
+
+// 12 B read + 8 B written per element (+ 4 B when the clip is active): a block's 4096 elements as 4 quads per thread.  16-byte
+// accesses where param, grad and buffer of the row are all 16-byte aligned and the quad lies inside the tensor (a block that
+// lies inside entirely issues its 12 loads before the first store), scalar accesses otherwise -- the rule of multi_sqnorm.
+__global__ __launch_bounds__(256) void multi_clip_sgd(const long long *__restrict__ table, int n, const float *__restrict__ norm,
+                                                      float max_norm, float lr, float momentum, float one_minus_dampening,
+                                                      float weight_decay, int nesterov, const float *__restrict__ sched) {
+  if (sched) lr = sched[0];   // (device schedule: the argument is a capture-time value)
+  const long long *row = opt_row(table, n, blockIdx.x);
+  float *p = reinterpret_cast<float *>(row[0]), *g = reinterpret_cast<float *>(row[1]);
+  float *m = reinterpret_cast<float *>(row[2]);          // (row[3] is not this kernel's: never read through)
+  const long long numel = row[4], base = (long long)((int)blockIdx.x - (int)row[5]) * kOptChunk;
+  const bool use_buf = momentum != 0.0f;
+  if (use_buf && m == nullptr) return;                   // (the host wrapper refuses such a table; nothing is dereferenced)
+  SgdArgs a;
+  a.coef = 1.0f;
+  if (max_norm > 0.0f) {
+    a.coef = max_norm / (norm[0] + 1e-6f);   // clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1
+    a.coef = a.coef >= 1.0f ? 1.0f : a.coef; // (a NaN norm stays a NaN coefficient, as torch.clamp leaves it)
+  }
+  a.scale = !(a.coef >= 1.0f);               // NaN scales too: every gradient, and with it every parameter, turns NaN as in torch
+  a.lr = lr;
+  a.momentum = momentum;
+  a.one_minus_dampening = one_minus_dampening;
+  a.weight_decay = weight_decay;
+  a.nesterov = nesterov != 0;
+  size_t align = reinterpret_cast<size_t>(p) | reinterpret_cast<size_t>(g);
+  if (use_buf) align |= reinterpret_cast<size_t>(m);
+  const bool vec = (align & 15) == 0;
+  if (vec && base + kOptChunk <= numel) {
+    float4 pv[4], gv[4], bv[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long i = base + (k * 256 + threadIdx.x) * 4;
+      pv[k] = *reinterpret_cast<const float4 *>(p + i);
+      gv[k] = *reinterpret_cast<const float4 *>(g + i);
+      bv[k] = use_buf ? *reinterpret_cast<const float4 *>(m + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long i = base + (k * 256 + threadIdx.x) * 4;
+      sgd_quad(a, pv[k], gv[k], bv[k]);
+      *reinterpret_cast<float4 *>(p + i) = pv[k];
+      if (a.scale) *reinterpret_cast<float4 *>(g + i) = gv[k];   // the gradient stays scaled, as after clip_grad_norm_
+      if (use_buf) *reinterpret_cast<float4 *>(m + i) = bv[k];
+    }
+    return;
+  }
+  for (int k = 0; k < 4; ++k) {
+    const long long i = base + (k * 256 + threadIdx.x) * 4;
+    if (i >= numel) break;
+    if (vec && i + 3 < numel) {
+      float4 pv = *reinterpret_cast<const float4 *>(p + i), gv = *reinterpret_cast<const float4 *>(g + i);
+      float4 bv = use_buf ? *reinterpret_cast<const float4 *>(m + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      sgd_quad(a, pv, gv, bv);
+      *reinterpret_cast<float4 *>(p + i) = pv;
+      if (a.scale) *reinterpret_cast<float4 *>(g + i) = gv;
+      if (use_buf) *reinterpret_cast<float4 *>(m + i) = bv;
+    } else {
+      for (int e = 0; e < 4 && i + e < numel; ++e) {
+        float pv = p[i + e], gv = g[i + e], bv = use_buf ? m[i + e] : 0.f;
+        sgd_element(a, pv, gv, bv);
+        p[i + e] = pv;
+        if (a.scale) g[i + e] = gv;
+        if (use_buf) m[i + e] = bv;
+      }
+    }
+  }
+}
+
 }  // namespace kgdet
 
 using namespace kgdet;
@@ -172,5 +282,35 @@ extern "C" int kgdet_multi_clip_adam_dev(const int64_t *table_dev, int32_t n, in
                      n, norm, max_norm, 0.0f, beta1, beta2, eps, weight_decay, 1.0f, 1.0f,
                      (float)(1.0 - (double)beta1_d), (float)(1.0 - (double)beta2_d), (const float *)sched);
   KGDET_CHECK_LAUNCH("multi_clip_adam_dev");
+  return KGDET_OK;
+}
+
+// clip + torch.optim.SGD (momentum, dampening, weight decay added to the gradient, Nesterov) over the same table, slot 2 = the
+// momentum buffer (0 only when momentum == 0), slot 3 ignored.  momentum and 1 - dampening are rounded from double once.
+extern "C" int kgdet_multi_clip_sgd(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm, float max_norm,
+                                    float lr, double momentum_d, double dampening_d, float weight_decay, int32_t nesterov,
+                                    void *stream) {
+  KGDET_CHECK_SHAPE(table_dev && n > 0 && total_blocks > 0 && total_blocks < (1LL << 31), "bad arguments");
+  KGDET_CHECK_SHAPE(max_norm <= 0.0f || norm, "a positive max_norm needs the norm");
+  hipLaunchKernelGGL(multi_clip_sgd, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const long long *)table_dev,
+                     n, norm, max_norm, lr, (float)momentum_d, (float)(1.0 - dampening_d), weight_decay, (int)nesterov,
+                     (const float *)nullptr);
+  KGDET_CHECK_LAUNCH("multi_clip_sgd");
+  return KGDET_OK;
+}
+
+// The same update with the learning rate read from device memory (see sgd_schedule_step): first the schedule advances
+// (sched[3] = steps taken so far on entry), then the update uses sched[0].
+extern "C" int kgdet_multi_clip_sgd_dev(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm,
+                                        float max_norm, float *sched, const float *lr_ring, int32_t ring, double momentum_d,
+                                        double dampening_d, float weight_decay, int32_t nesterov, void *stream) {
+  KGDET_CHECK_SHAPE(table_dev && n > 0 && total_blocks > 0 && total_blocks < (1LL << 31) && sched, "bad arguments");
+  KGDET_CHECK_SHAPE(max_norm <= 0.0f || norm, "a positive max_norm needs the norm");
+  KGDET_CHECK_SHAPE(lr_ring == nullptr || ring > 0, "empty learning-rate ring");
+  hipLaunchKernelGGL(sgd_schedule_step, dim3(1), dim3(64), 0, (hipStream_t)stream, sched, lr_ring, (int)ring);
+  hipLaunchKernelGGL(multi_clip_sgd, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream, (const long long *)table_dev,
+                     n, norm, max_norm, 0.0f, (float)momentum_d, (float)(1.0 - dampening_d), weight_decay, (int)nesterov,
+                     (const float *)sched);
+  KGDET_CHECK_LAUNCH("multi_clip_sgd_dev");
   return KGDET_OK;
 }

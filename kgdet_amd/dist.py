@@ -398,7 +398,8 @@ class DistOptimizerHook(object):
         self.force_distributed = force_distributed
         self._reducer = None
         self._params = None
-        self._fused = None
+        self._fused = None          # optim.FusedClipAdam
+        self._fused_sgd = None      # optim.FusedClipSGD
         self._local_only = False
 
     def set_local_only(self, flag):
@@ -430,25 +431,33 @@ class DistOptimizerHook(object):
         if self._params is None:    # model.parameters() walks every module: 1 ms of Python per step
             self._params = [p for p in model.parameters() if p.requires_grad]
         if self._fused is None:
-            from .optim import FusedClipAdam
+            from .optim import FusedClipAdam, FusedClipSGD
             self._fused = FusedClipAdam()
+            self._fused_sgd = FusedClipSGD()
+        fused = None
         if len(optimizer.param_groups) == 1 and self._fused.applicable(optimizer, self._params, self.grad_clip):
-            # clip + Adam as two multi-tensor HIP passes (csrc/optim.hip); the first step (no state yet) and anything else: torch
-            # (device-side schedule -- FusedClipAdam.enable_device_schedule, the graphed step of runner.GraphedTrainStep --: the
-            #  learning rate is published and the step counted by the host around the launch; inside a capture the replaying
+            fused = self._fused
+        elif self._fused_sgd.applicable(optimizer, self._params, self.grad_clip):
+            fused = self._fused_sgd
+        if fused is not None:
+            # clip + Adam / momentum SGD as two multi-tensor HIP passes (csrc/optim.hip); the first step (no state yet) and anything
+            # else: torch
+            # (device-side schedule -- enable_device_schedule of the fused object, the graphed step of runner.GraphedTrainStep --:
+            #  the learning rate is published and the step counted by the host around the launch; inside a capture the replaying
             #  caller does both)
-            dev_sched = self._fused._sched is not None and not torch.cuda.is_current_stream_capturing()
+            dev_sched = fused._sched is not None and not torch.cuda.is_current_stream_capturing()
             if dev_sched:
-                self._fused.publish_lr(optimizer)
-            if self._fused.step(optimizer, self._params, self.grad_clip):
+                fused.publish_lr(optimizer)
+            if fused.step(optimizer, self._params, self.grad_clip):
                 if dev_sched:
-                    self._fused.step_published()
+                    fused.step_published()
                 return
         # torch advances the step counters below: the fused path re-reads them next time; a device-side schedule is folded back
         # into the optimizer's counters first (otherwise they would lag by the steps it took, and its own count would miss this one)
-        if getattr(self._fused, '_sched', None) is not None and not torch.cuda.is_current_stream_capturing():
-            self._fused.disable_device_schedule(optimizer)
-        self._fused.invalidate()
+        for f in (self._fused, self._fused_sgd):
+            if getattr(f, '_sched', None) is not None and not torch.cuda.is_current_stream_capturing():
+                f.disable_device_schedule(optimizer)
+            f.invalidate()
         if self.grad_clip is not None:
             self.clip_grads(self._params)
         optimizer.step()

@@ -255,14 +255,16 @@ def multi_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1,
 
 
 class GraphedTrainStep(object):
-    """One training step of a FIXED-shape batch -- forward, the nine losses, backward, gradient clip, Adam (or torch's fused
-    SGD: config 5) -- as ONE HIP graph.
+    """One training step of a FIXED-shape batch -- forward, the nine losses, backward, gradient clip, Adam or momentum SGD (the
+    project's fused steps, or torch's fused SGD when the optimizer was built with ``fused=True``: config 5) -- as ONE HIP graph.
 
     The eager step is ~560 kernel launches whose enqueue (Python module calls + launch latency, ~11 ms at full size) takes as
     long as the GPU needs to run them (``tools/host_step_cost.py``): every kernel gain below a few percent is invisible in
     images/s.  Nothing in the step reads back to the host (``tests/test_gpu_head.py::test_training_step_has_no_host_syncs``), the
     optimizer's schedule lives in device memory (``optim.FusedClipAdam.enable_device_schedule``: step count, bias corrections
-    and the learning rate are not kernel arguments), so the whole step is captured once (``torch.cuda.CUDAGraph`` = hipGraph)
+    and the learning rate are not kernel arguments; ``optim.FusedClipSGD`` likewise with the learning rate alone, so a plain
+    ``torch.optim.SGD`` as ``build_optimizer`` makes it from the DeepFashion2 configs is captured too), so the whole step is
+    captured once (``torch.cuda.CUDAGraph`` = hipGraph)
     and replayed per iteration.  The reference has no equivalent (``mmdet/apis/train.py:17-134`` + mmcv's Runner issue every
     op eagerly); the arithmetic is the eager step's, kernel by kernel.
 
@@ -278,7 +280,7 @@ class GraphedTrainStep(object):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             raise NotImplementedError('the graphed step covers one rank; a multi-rank job exchanges gradients eagerly')
-        from .optim import FusedClipAdam
+        from .optim import FusedClipAdam, FusedClipSGD
         self.model, self.optimizer, self.hook = model, optimizer, opt_hook
         self.static = batch
         self.static_tensors = [batch['img']] + [t for k in ('gt_bboxes', 'gt_labels', 'gt_keypoints') for t in batch.get(k, [])]
@@ -297,13 +299,19 @@ class GraphedTrainStep(object):
             for _ in range(max(int(warmup), 2)):      # optimizer state, weight-image sets, MIOpen find: all before the capture
                 one_step()
         torch.cuda.current_stream().wait_stream(side)
-        fused = opt_hook._fused
+        fused, fused_sgd = opt_hook._fused, getattr(opt_hook, '_fused_sgd', None)
         self.fused, self.lr_t = None, None
         if fused is not None and len(optimizer.param_groups) == 1 and \
                 FusedClipAdam.applicable(optimizer, opt_hook._params, opt_hook.grad_clip):
             if fused._sched is None:
                 fused.enable_device_schedule(optimizer)
             self.fused = fused
+        elif fused_sgd is not None and FusedClipSGD.applicable(optimizer, opt_hook._params, opt_hook.grad_clip):
+            # plain torch.optim.SGD (the DeepFashion2 configs): the project's clip + SGD step with the rate in device memory, fed
+            # through the page-locked ring -- a rate change (every step of the warm-up) costs no synchronisation
+            if fused_sgd._sched is None:
+                fused_sgd.enable_device_schedule(optimizer)
+            self.fused = fused_sgd
         elif (type(optimizer) is torch.optim.SGD and len(optimizer.param_groups) == 1
               and optimizer.param_groups[0].get('fused') and not optimizer.param_groups[0].get('nesterov')):
             # torch's fused SGD (config 5: momentum 0.9, weight decay 1e-4) keeps no step count; with the learning rate as a
@@ -316,8 +324,9 @@ class GraphedTrainStep(object):
             self.lr_pin = torch.tensor([float(group['lr'])], dtype=torch.float32).pin_memory()
             self._lr_last = float(group['lr'])
         else:
-            raise NotImplementedError('the graphed step needs the fused clip + Adam step or torch.optim.SGD(fused=True) '
-                                      '(one parameter group)')
+            raise NotImplementedError('the graphed step needs the fused clip + Adam step, the fused clip + SGD step (a plain '
+                                      'torch.optim.SGD on CUDA fp32 parameters) or torch.optim.SGD(fused=True) without Nesterov '
+                                      'momentum -- one parameter group in every case')
         group = optimizer.param_groups[0]
         lr_host = group['lr']
         if self.lr_t is not None:
@@ -343,7 +352,8 @@ class GraphedTrainStep(object):
         new = [batch['img']] + [t for k in ('gt_bboxes', 'gt_labels', 'gt_keypoints') for t in batch.get(k, [])]
         if len(new) != len(self.static_tensors) or any(a.shape != b.shape for a, b in zip(new, self.static_tensors)):
             raise ValueError('the graphed step was captured for other tensor shapes')
-        if self.lr_t is not None:
+        if self.lr_t is not None or type(self.optimizer) is torch.optim.SGD:
+            # (every SGD optimizer, whichever step it takes)
             # Observed on this stack (ROCm 7.0 / torch 2.10, tools/graph_serial_probe.py): an eager kernel enqueued BEHIND an in-flight
             # replay of the config-5 (serial head, SGD) graph ends in an HSA hardware exception (0x1016) -- the KGDet graph takes the
             # same pattern without complaint (tools/graph_load_probe.py), a replay that has finished is fine in both.  Cause not
