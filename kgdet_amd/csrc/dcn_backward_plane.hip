@@ -53,6 +53,7 @@ size_t dcn_bwd_input_plane_lds_bytes(int parts, int plane_pixels) {
 #ifndef KGDET_HOT_MIN
 #define KGDET_HOT_MIN 64   // contributions above which a cell becomes a column of dcn_hot_gemm
 #endif
+static_assert(KGDET_HOT_MIN == 64, "dcn_inv_medium_sums and the cluster rule of dcn_inv_overflow_sums hard-code 64 contributions");
 template <int THREADS>
 __device__ __forceinline__ void build_inverse_taps_body(const DcnProblem &p, uint4 *__restrict__ inv, int *__restrict__ hdr,
                                                         DcnInvOvfCell *__restrict__ cells, int2 *__restrict__ spill,
