@@ -21,7 +21,7 @@ from .layers import build_conv_layer, build_norm_layer, constant_init, kaiming_i
 from .registry import BACKBONES
 
 
-STEM_CONV = _os.environ.get('KGDET_STEM_CONV', '1') == '1'    # csrc/conv1x1.hip stem_conv7x7_s2 (0: MIOpen; A/B)
+STEM_CONV = _os.environ.get('KGDET_STEM_CONV', '1') == '1'    # csrc/dense_forward.hip stem_conv7x7_s2 (0: MIOpen; A/B)
 _stem_cache = {}
 
 

@@ -1,5 +1,5 @@
 """The model / train / test settings of the reference's KGDet configs as plain dicts, for use on
-machines where the reference tree is not mounted (the GPU box).  tests/test_config.py checks them
+machines where the reference tree is not mounted (the GPU box).  tests/test_host_logic.py checks them
 against R/configs/kgdet_moment_r50_fpn_1x-demo.py and
 R/configs/reppoints_moment_serial_r50_fpn_1x-deepfashion2.py whenever the reference is present.
 """

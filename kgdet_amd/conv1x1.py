@@ -1,5 +1,5 @@
 """1x1 and 3x3 (stride 1, padding 1) convolutions, fp32 NCHW, on the bf16 hi/lo-split MFMA GEMM kernels
-(csrc/conv1x1.hip).
+(csrc/dense_forward.hip, csrc/dense_grad_weight.hip).
 
 ``conv_split(x, weight)`` equals ``F.conv2d(x, weight, padding=k // 2)`` for a ``[O, C, k, k]`` weight, k in {1, 3},
 to fp32-level accuracy (~5e-6 of the output scale), forward and both gradients; used by the backbone's bottlenecks
@@ -98,7 +98,7 @@ def _stream():
 
 
 # Operand format of the FORWARD images (activations x weights): two fp16 parts (22 mantissa bits, fp32-class results) instead of
-# two bf16 parts (16 bits) -- csrc/conv1x1.hip split_pair_t.  The packed tensor carries the format as an attribute
+# two bf16 parts (16 bits) -- csrc/dense_common.h split_pair_t.  The packed tensor carries the format as an attribute
 # (`kgdet_f16`), `_apply` reads it; transposed (grad_input) images and the weight-gradient kernels stay bf16: gradients need
 # the exponent range.  KGDET_CONV_FWD_F16=0: bf16 parts everywhere (A/B, and round 2's arithmetic).
 FORWARD_F16 = _os.environ.get('KGDET_CONV_FWD_F16', '1') == '1'
@@ -609,7 +609,7 @@ class _ConvSplitStride2(torch.autograd.Function):
         gy = gy.contiguous()
         gx = None
         if ctx.needs_input_grad[0] and STRIDE2_GRAD_INPUT and weight.shape[0] % 16 == 0:
-            # the four parity classes of the output pixels on the patch kernel (csrc/conv1x1.hip conv3x3_s2_grad_input)
+            # the four parity classes of the output pixels on the patch kernel (csrc/dense_forward.hip conv3x3_s2_grad_input)
             img_t = ctx.img_t if ctx.img_t is not None else _pack(weight, True)
             gx = torch.empty_like(x)
             _lib.check(_lib_sizes().kgdet_conv3x3_s2_grad_input(
@@ -620,7 +620,7 @@ class _ConvSplitStride2(torch.autograd.Function):
         need_gw = ctx.needs_input_grad[1]
         if need_gw and STRIDE2_GRAD_WEIGHT and (weight.shape[0] * weight.shape[1]) % 2 == 0:
             # the nine strided views of x gathered once, then the 1x1 weight-gradient GEMM over (tap, channel) columns
-            # (csrc/conv1x1.hip kgdet_conv3x3_s2_grad_weight): MIOpen's igemm_wrw + its layout transposes were the last vendor
+            # (csrc/dense_grad_weight.hip kgdet_conv3x3_s2_grad_weight): MIOpen's igemm_wrw + its layout transposes were the last vendor
             # kernels of the training step
             L = _lib_sizes()
             B, C, H, W = x.shape

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void bn_partial_sum(const float *__restrict__ 
 }
 
 // ---- BatchNorm folded into the convolution (kgdet_amd/backbone.py _ConvBNActFold) ---------------------------------------
-// forward:  z = [relu](conv(x, w * s) + t [+ r])  in the convolution's store (csrc/conv1x1.hip), y = conv(x, w) is never formed.
+// forward:  z = [relu](conv(x, w * s) + t [+ r])  in the convolution's store (csrc/dense_forward.hip), y = conv(x, w) is never formed.
 // backward: g' = g * [z > 0]  (this kernel; it also IS the residual branch's gradient), grad_x = conv_grad_input(g', w * s),
 //           G = conv_grad_weight(x, g'), grad_w = s (.) G, grad_beta = sum g',
 //           grad_gamma = invstd * (sum g' * y - mean * sum g')  with  sum_p g'[o, p] * y[o, p] = <w[o], G[o]>  (bn_fold_finish) --

@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/kgdet_hip.h"
 
@@ -43,5 +44,30 @@ int cu_count();  // cached multiProcessorCount of the current device
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// Environment switches (A/B measurement, overrides for the timing tools, test hooks; none is part of the API).  Every file
+// that reads some lists them in a table at its top.
+static inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline bool env_present(const char *name) { return getenv(name) != nullptr; }
+
+// Raise the dynamic-LDS limit of the given kernels to `bytes`, once per thread and kernel.  A failure is reported (and tried
+// again by the next call): `if (int rc = allow_lds<...>(bytes)) return rc;`
+template <auto Kernel>
+int allow_lds_one(size_t bytes) {
+  static thread_local bool done = false;
+  if (done) return KGDET_OK;
+  KGDET_HIP_TRY(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  done = true;
+  return KGDET_OK;
+}
+template <auto... Kernels>
+int allow_lds(size_t bytes) {
+  int rc = KGDET_OK;
+  (void)(((rc = allow_lds_one<Kernels>(bytes)) == KGDET_OK) && ...);
+  return rc;
+}
 
 }  // namespace kgdet

@@ -29,30 +29,7 @@ namespace kgdet {
 
 namespace {
 
-int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-bool env_present(const char *name) { return getenv(name) != nullptr; }
-
 constexpr size_t kMaxLds = 160 * 1024;
-
-// Raise the dynamic-LDS limit of the given kernels to `bytes`, once per thread and kernel.  A failure is reported (and tried
-// again by the next call): `if (int rc = allow_lds<...>(bytes)) return rc;`
-template <auto Kernel>
-int allow_lds_one(size_t bytes) {
-  static thread_local bool done = false;
-  if (done) return KGDET_OK;
-  KGDET_HIP_TRY(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  done = true;
-  return KGDET_OK;
-}
-template <auto... Kernels>
-int allow_lds(size_t bytes) {
-  int rc = KGDET_OK;
-  (void)(((rc = allow_lds_one<Kernels>(bytes)) == KGDET_OK) && ...);
-  return rc;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Shapes, eligibility, table sizes

@@ -8,7 +8,7 @@
 //
 // Here, with 288 GB of HBM, the column gradient IS materialised once -- transposed, channels innermost:
 //     colT[b][p][t*C + c] = sum_o grad_out[b][o][p] * W[o][c][t]                                  (310 MB at 2x100x168)
-// as ONE split-bf16 MFMA GEMM per image on the backbone's 1x1-convolution kernel (conv_nn<1>, csrc/conv1x1.hip) with
+// as ONE split-bf16 MFMA GEMM per image on the backbone's 1x1-convolution kernel (conv_nn<1>, csrc/dense_forward.hip) with
 // the pixels in the role of output channels (A = grad_out^T packed as a weight image, "image" = the permuted weight),
 // and both consumers read it in 1 KB runs:
 //   * grad_offset: one workgroup per output pixel, a thread per channel: colT row x the four corner rows of x^T

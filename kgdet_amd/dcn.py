@@ -100,7 +100,7 @@ _EXACT_BACKWARD = False
 class arithmetic(object):
     """``with dcn.arithmetic('exact'):`` -- the whole step in plain fp32 arithmetic: deformable forward on the
     f32-input MFMA kernel, deformable backward on the exact-fp32 kernels (instead of the split-bf16 plane kernels) and
-    the dense convolutions on MIOpen's fp32 kernels (instead of csrc/conv1x1.hip).  ``'split'`` is the default
+    the dense convolutions on MIOpen's fp32 kernels (instead of csrc/dense_forward.hip, csrc/dense_grad_weight.hip).  ``'split'`` is the default
     everywhere.  Used to measure what the hi/lo split costs in accuracy over a whole training step."""
 
     def __init__(self, mode):

@@ -245,7 +245,7 @@ class ConvModule(nn.Module):
                 conv = self.conv
                 if (type(conv) is nn.Conv2d and conv.bias is None and torch.is_grad_enabled()
                         and conv1x1.applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
-                    x = conv1x1.conv_split(x, conv.weight)     # fp32 training: split-operand MFMA kernels (conv1x1.hip)
+                    x = conv1x1.conv_split(x, conv.weight)     # fp32 training: split-operand MFMA kernels (csrc/dense_forward.hip)
                 elif (type(conv) is nn.Conv2d and conv.bias is None and torch.is_grad_enabled()
                         and conv1x1.odd_map_applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
                     x = conv1x1.unpad_odd(conv1x1.conv_split(conv1x1.pad_odd(x), conv.weight), x.shape[3])

@@ -356,7 +356,7 @@ def test_resnet_with_dcn_stages_builds_and_steps():
                                        (2, 128, 128, 30, 44), (2, 256, 128, 9, 84), (1, 128, 256, 7, 4),
                                        (2, 512, 128, 100, 168), (2, 64, 2048, 25, 42), (2, 128, 128, 100, 168)])
 def test_conv1x1_split_matches_fp64_convolution(B, C, O, H, W, k, monkeypatch):
-    """csrc/conv1x1.hip (bf16 hi/lo-split MFMA GEMMs): forward, grad_input and grad_weight against the fp64
+    """csrc/dense_forward.hip, csrc/dense_grad_weight.hip (bf16 hi/lo-split MFMA GEMMs): forward, grad_input and grad_weight against the fp64
     convolution, to fp32-level accuracy (1e-5 of the result's scale; MIOpen's fp32 kernels sit at ~1e-6); ragged
     pixel tiles, M < 128, the K-split and the 8- and 16-byte load variants of grad_weight; the last three shapes take the
     160-pixel tiles (264 / 288 tiles of 128 pixels: conv_nn<1, 5>, conv3x3_patch4<4, 5>)."""
@@ -523,7 +523,7 @@ def test_conv1x1_not_applicable_cases_fall_back():
 @pytest.mark.parametrize('H,W', [(13, 21), (7, 11), (5, 5), (3, 3), (2, 2), (25, 42), (9, 6)])
 @pytest.mark.parametrize('k', [1, 3])
 def test_split_convolutions_take_odd_and_unaligned_maps_in_place(H, W, k):
-    """csrc/conv1x1.hip on maps whose pixel count is odd / whose rows are not a multiple of 4 floats (the two coarsest levels of a
+    """csrc/dense_forward.hip, csrc/dense_grad_weight.hip on maps whose pixel count is odd / whose rows are not a multiple of 4 floats (the two coarsest levels of a
     five-level head, 13 x 21 and 7 x 11; the 25 x 42 head maps): forward, grad_input and grad_weight (conv_ntp: a tap is a shift
     of a 4-byte aligned 16-byte load, ragged last pieces moved back into place) against torch's float64 convolution, and the
     biased convolution + ReLU of config 5's FPN.  Rounds 2-3 appended a zero column around every such convolution."""
@@ -575,7 +575,7 @@ def test_conv3x3_stride2_forward_matches_fp64(B, C, O, H, W):
     xd, wd = x.detach().double().requires_grad_(), w.detach().double().requires_grad_()
     F.conv2d(xd, wd, stride=2, padding=1).backward(gy.double())
     assert ((x.grad.double() - xd.grad).abs().max() / xd.grad.abs().max()).item() < 1e-5
-    # (round 6: grad_weight on the gather + 1x1 weight-gradient GEMM, csrc/conv1x1.hip kgdet_conv3x3_s2_grad_weight)
+    # (round 6: grad_weight on the gather + 1x1 weight-gradient GEMM, csrc/dense_grad_weight.hip kgdet_conv3x3_s2_grad_weight)
     assert ((w.grad.double() - wd.grad).abs().max() / wd.grad.abs().max()).item() < 1e-5
     assert torch.isfinite(x.grad).all() and torch.isfinite(w.grad).all()
     x.grad = None; w.grad = None
@@ -759,11 +759,14 @@ def test_gate_fusion_step_equals_the_separate_mask_passes():
 @pytest.mark.gpu
 @pytest.mark.parametrize('B,C,O,H,W,k', [(2, 128, 512, 20, 36, 1), (2, 512, 128, 25, 42, 1), (1, 64, 256, 13, 21, 1), (2, 256, 64, 100, 168, 1),
                                          (2, 128, 128, 20, 36, 3), (2, 256, 256, 25, 42, 3), (1, 128, 128, 13, 21, 3),
-                                         (2, 128, 128, 100, 168, 3), (3, 128, 200, 9, 12, 1)])
+                                         (2, 128, 128, 100, 168, 3), (3, 128, 200, 9, 12, 1),
+                                         (2, 64, 128, 1, 3, 1), (1, 128, 128, 5, 3, 3)])
 def test_weight_gradient_kernels_sum_the_rows_of_grad_y(B, C, O, H, W, k):
     """kgdet_conv*_grad_weight_fold with bn_partial == NULL: grad_beta / grad_gamma from row sums formed inside the
     weight-gradient kernel (conv_nt8 / conv_ntp, aligned and ragged maps) equal those from kgdet_bn_fold_backward's partials,
-    the weight gradient itself is bit-identical, and both match float64."""
+    the weight gradient itself is bit-identical, and both match float64.  The last two maps have fewer than four pixels
+    (1x1) / fewer than four columns (3x3): conv_ntp does not take them, and conv_nt8 runs on pad_rows2's zero-padded copies
+    (csrc/dense_grad_weight.hip plan_gw)."""
     from kgdet_amd import backbone as bb, conv1x1 as c1, _lib
     g = torch.Generator(device='cpu').manual_seed(B * C + H + k)
     x = torch.randn(B, C, H, W, generator=g).cuda()
@@ -855,7 +858,7 @@ def test_step_scope_packs_follow_weight_updates():
 @pytest.mark.gpu
 @pytest.mark.parametrize('xs,ws,tol', [(1.0, 0.03, 1e-6), (100.0, 0.03, 1e-6), (1.0, 1.0, 1e-6), (1e-3, 0.03, 1e-4), (1e-5, 0.03, 1e-2)])
 def test_fp16_forward_parts_envelope(xs, ws, tol):
-    """The forward operands of the dense convolutions are split into two fp16 parts (csrc/conv1x1.hip split_pair_t, weights
+    """The forward operands of the dense convolutions are split into two fp16 parts (csrc/dense_common.h split_pair_t, weights
     pre-scaled by 2^8): fp32-class results (<= 1e-6 of the output scale against float64; the bf16 parts gave 5e-6) for
     activations of magnitude ~1e-2 .. 6e4 and weights up to 255 -- what BatchNorm / GroupNorm-normalised networks produce.
     Below that the lo part of an activation becomes an fp16 subnormal and the error floor is an ABSOLUTE ~3e-8 per activation:
@@ -879,7 +882,7 @@ def test_fp16_forward_parts_envelope(xs, ws, tol):
 def test_fp16_forward_parts_saturate_instead_of_nan():
     """Round-3 ADVICE (medium): an operand beyond fp16's range used to become hi = inf, lo = v - inf = -inf and the MFMA sum
     inf + (-inf) = NaN poisoned the whole output channel.  The fp16-part kernels now run with the MODE register's FP16_OVFL
-    bit set (csrc/conv1x1.hip f16_saturate_on): a part beyond +/-65504 is clamped, so (a) activations up to 131008 = 2 x
+    bit set (csrc/dense_common.h f16_saturate_on): a part beyond +/-65504 is clamped, so (a) activations up to 131008 = 2 x
     65504 are still represented by hi + lo -- hi = 65504 and a LARGE lo part, i.e. with the 11 bits of one fp16 number
     (measured 2e-4 of the output scale; fp32-class accuracy ends at 65504 as documented) --, (b) a folded BatchNorm channel with a
     tiny running variance (var = 1e-12, gamma = 1: w * s ~ 3e3 beyond the 255 the 2^8-scaled image holds) gives a FINITE,

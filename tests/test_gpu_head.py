@@ -668,7 +668,7 @@ def test_full_size_training_step_matches_float64(mode, golden_dir):
     accurate to 4.7e-6 .. 8.9e-6, which the focal-loss gradient of the classification tower (a small difference of large
     sums: amplification ~1000, fp32 itself shows 1.5e-4 there) turns into percents -- and nothing from the split backward or
     the deformable kernels (<= 6e-5).  The FORWARD operands of the dense convolutions are therefore split into two fp16 parts
-    now (22 mantissa bits, same MFMA rate and instruction count, csrc/conv1x1.hip split_pair_t): forward features 3.4e-7 ..
+    now (22 mantissa bits, same MFMA rate and instruction count, csrc/dense_common.h split_pair_t): forward features 3.4e-7 ..
     1.2e-6 against MIOpen fp32, gradient norms of every parameter tensor within 3.3e-5 of float64, no measurable cost
     (141.5 vs 142.5 img/s, same box).  The bounds below are those measurements with head room; BASELINE.md's 1e-3 holds for the fp32 mode and for every deformable-kernel gradient."""
     from kgdet_amd import dcn

@@ -1,5 +1,5 @@
 """Aggregate roofline of the backbone / tower convolution kernels in one training step: enumerates the convolutions that
-run on csrc/conv1x1.hip (by shape rule of kgdet_amd/conv1x1.applicable), sums their algorithmic flops and bytes, and divides
+run on csrc/dense_forward.hip / dense_grad_weight.hip (by shape rule of kgdet_amd/conv1x1.applicable), sums their algorithmic flops and bytes, and divides
 by the per-step kernel times of a committed step profile:  python tools/conv_roofline.py <train_steady.md>"""
 import re
 import sys
