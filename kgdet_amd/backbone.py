@@ -6,7 +6,7 @@ the optional deformable ``conv2`` + ``conv2_offset`` of the dcn configs, :162-18
 contract (``conv1``, ``bn1``, ``layer{1..4}.{i}.conv{1,2,3}|bn{1,2,3}|downsample.{0,1}``).
 BatchNorm stays in eval mode (``norm_eval``) and ``frozen_stages`` freezes the stem + first stages.
 """
-import ctypes
+import collections
 import os as _os
 import weakref
 
@@ -15,14 +15,27 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from . import conv1x1
+from . import _lib, conv1x1
 from . import dcn as dcn_ops
 from .layers import build_conv_layer, build_norm_layer, constant_init, kaiming_init
 from .registry import BACKBONES
 
 
-STEM_CONV = _os.environ.get('KGDET_STEM_CONV', '1') == '1'    # csrc/dense_forward.hip stem_conv7x7_s2 (0: MIOpen; A/B)
+# ---- switches (the other setting of each, and who uses it) ----------------------------------------------------------------
+STEM_CONV = _os.environ.get('KGDET_STEM_CONV', '1') == '1'   # 0: conv1 of a frozen stem on MIOpen (tools/step_vs_f64.py)
+FUSE_STEM = _os.environ.get('KGDET_FUSE_STEM', '1') == '1'   # 0 / False: conv_bn + nn.MaxPool2d (the tests compare the two)
+MERGE_CONV_BN = True    # False: two autograd nodes (conv_split, frozen_bn_act) -- the tests compare the two
+RAW_BRANCHES = _os.environ.get('KGDET_RAW_BRANCHES', '1') == '1'   # 0: downsample / stride-2 conv2 take their own bias pass at bf16 inference (the tests compare the two)
+GATE_FUSION = _os.environ.get('KGDET_GATE_FUSION', '1') == '1'    # 0: every ReLU node masks its own gradient (the tests compare the two)
+# KGDET_GEMM_CHOICES=<file.json>: the measured bf16 inference routes are read from / written to the file (_load_gemm_choices)
+
+_L = conv1x1._library      # the library with its prototypes declared: plain ints, data_ptr() and None as arguments
+_bn_fold_lib = _L           # (the name under which the tests reach it)
 _stem_cache = {}
+
+
+def _p(t):
+    return t.data_ptr() if t is not None else None
 
 
 def _stem_conv(conv, x):
@@ -40,12 +53,11 @@ def _stem_conv(conv, x):
             w160[:, :147] = w.detach().reshape(64, 147)
             hit = (key, conv1x1._pack(w160.view(64, 160, 1, 1), False), weakref.ref(w))
             _stem_cache[id(conv)] = hit
-        from . import _lib
         B, _, H, W = x.shape
         y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().kgdet_stem_conv7x7_s2_fmt(
-            _lib.ptr(hit[1]), _lib.ptr(x), _lib.ptr(y), ctypes.c_int64(B), ctypes.c_int32(H), ctypes.c_int32(W),
-            ctypes.c_int32(1 if getattr(hit[1], 'kgdet_f16', False) else 0), _lib.current_stream()), 'stem_conv7x7_s2')
+        _lib.check(_L().kgdet_stem_conv7x7_s2_fmt(hit[1].data_ptr(), x.data_ptr(), y.data_ptr(), B, H, W,
+                                                  1 if getattr(hit[1], 'kgdet_f16', False) else 0, _lib.raw_stream()),
+                   'stem_conv7x7_s2')
         return y
     return conv(x).contiguous()
 
@@ -90,8 +102,10 @@ class BasicBlock(nn.Module):
         return self.relu(out)
 
 
-_FUSE_EPI = _os.environ.get('KGDET_FUSE_EPI', '1') == '1'   # fp32 inference: epilogue inside conv_nn's store (0: separate pass, for A/B)
-_fold_cache = {}   # id(conv) -> (weakref to conv, folded weight, folded bias)
+# inference: a convolution with its frozen BatchNorm folded in -- weakref to the conv, w * s, t in fp32, the operand image of
+# w * s (fp32 on the split kernels) or None, the parameters' version counters, t in bf16 (bf16 inference) or None
+_Folded = collections.namedtuple('_Folded', 'conv weight bias packed version bias16')
+_fold_cache = {}   # (id(conv), bf16?) -> _Folded
 
 
 def clear_fold_cache():
@@ -112,12 +126,9 @@ def _epilogue_(y, bias, residual, relu):
             fmt = None
         if fmt is not None and (residual is None or (residual.dtype == y.dtype and residual.shape == y.shape
                                                      and residual.is_contiguous(memory_format=fmt))):
-            from . import _lib
-            _lib.check(_lib.lib().kgdet_bias_act(
-                _lib.ptr(y), _lib.ptr(bias), _lib.ptr(residual), ctypes.c_int64(N), ctypes.c_int32(C),
-                ctypes.c_int64(y.numel() // max(N * C, 1)), ctypes.c_int32(0 if y.dtype == torch.float32 else 1),
-                ctypes.c_int32(1 if relu else 0), ctypes.c_int32(1 if fmt is torch.channels_last else 0),
-                _lib.current_stream()), 'bias_act')
+            _lib.check(_L().kgdet_bias_act(
+                y.data_ptr(), _p(bias), _p(residual), N, C, y.numel() // max(N * C, 1), 0 if y.dtype == torch.float32 else 1,
+                1 if relu else 0, 1 if fmt is torch.channels_last else 0, _lib.raw_stream()), 'bias_act')
             return y
     if bias is not None:
         y = y + bias.to(y.dtype).view(1, -1, 1, 1)
@@ -126,38 +137,11 @@ def _epilogue_(y, bias, residual, relu):
     return F.relu(y, inplace=True) if relu else y
 
 
-_BN = None
-_bn_partials = {}
-
-
-def _bn_lib():
-    """bn_act entry points with argtypes declared once (plain ints / pointers marshal faster than c_* objects)"""
-    global _BN
-    if _BN is None:
-        from . import _lib
-        L = _lib.lib()
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        L.kgdet_bn_act_partials.restype, L.kgdet_bn_act_partials.argtypes = ctypes.c_int32, [i64, i32, i64]
-        L.kgdet_bn_act_forward.restype = ctypes.c_int
-        L.kgdet_bn_act_forward.argtypes = [vp, vp, vp, vp, vp, f32, vp, vp, i64, i32, i64, i32, vp]
-        L.kgdet_bn_act_backward.restype = ctypes.c_int
-        L.kgdet_bn_act_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, i64, i32, i64, vp]
-        L.kgdet_bn_relu_maxpool.restype = ctypes.c_int
-        L.kgdet_bn_relu_maxpool.argtypes = [vp, vp, vp, vp, vp, f32, vp, i64, i32, i32, i32, vp]
-        _BN = L
-    return _BN
-
-
-def _p(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _bn_act_forward(x, gamma, beta, mean, var, eps, residual, relu):
-    from . import _lib
     N, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(N * C, 1)
     y = torch.empty_like(x)
-    _lib.check(_bn_lib().kgdet_bn_act_forward(
+    _lib.check(_L().kgdet_bn_act_forward(
         _p(x), _p(gamma), _p(beta), _p(mean), _p(var), eps, _p(residual), _p(y), N, C, HW, 1 if relu else 0,
         _lib.raw_stream(x.device.index)), 'bn_act_forward')
     return y
@@ -165,19 +149,15 @@ def _bn_act_forward(x, gamma, beta, mean, var, eps, residual, relu):
 
 def _bn_act_backward(gy, x, y, gamma, beta, mean, var, eps, has_res, relu, need_gx):
     """-> (grad_x or None, grad_residual-or-None (None: it IS gy), [grad_beta, grad_gamma] sums [2, C])"""
-    from . import _lib
     N, C = x.shape[0], x.shape[1]
     HW = x.numel() // max(N * C, 1)
-    L = _bn_lib()
-    P = _bn_partials.get((N, C, HW))
-    if P is None:
-        P = _bn_partials[(N, C, HW)] = L.kgdet_bn_act_partials(N, C, HW)
+    P = conv1x1._size('kgdet_bn_act_partials', N, C, HW)
     partial = torch.empty((2, C, max(P, 1)), dtype=torch.float32, device=x.device)
     gx = torch.empty_like(x) if need_gx else None
     masked = has_res and relu
     gres = torch.empty_like(x) if masked else None
     sums = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    _lib.check(L.kgdet_bn_act_backward(
+    _lib.check(_L().kgdet_bn_act_backward(
         _p(gy), _p(x), _p(y), _p(gamma), _p(beta), _p(mean), _p(var), eps, 1 if has_res else 0, 1 if relu else 0,
         _p(gx), _p(gres), _p(partial), _p(sums), N, C, HW, _lib.raw_stream(x.device.index)), 'bn_act_backward')
     return gx, gres, sums
@@ -247,23 +227,6 @@ class _ConvBNAct(torch.autograd.Function):
         return gx, gw, ggamma, gbeta, None, None, None, gres, None, None
 
 
-def _bn_fold_lib():
-    L = _bn_lib()
-    if not hasattr(L, '_kgdet_fold_ready'):
-        vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-        L.kgdet_bn_fold_backward.restype = ctypes.c_int
-        L.kgdet_bn_fold_backward.argtypes = [vp, vp, i32, vp, vp, i64, i32, i64, vp]
-        L.kgdet_bn_fold_finish.restype = ctypes.c_int
-        L.kgdet_bn_fold_finish.argtypes = [vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, vp]
-        L._kgdet_fold_ready = True
-    return L
-
-
-NHWC_EXTENDED = _os.environ.get('KGDET_NHWC_EXTENDED', '1') == '1'
-RAW_BRANCHES = _os.environ.get('KGDET_RAW_BRANCHES', '1') == '1'   # 0: downsample / stride-2 conv2 take their own bias pass at bf16 inference (A/B)
-GATE_FUSION = _os.environ.get('KGDET_GATE_FUSION', '1') == '1'    # 0: every ReLU node masks its own gradient (A/B)
-
-
 class _GateLink(object):
     """Hand-over between two ``_ConvBNActFold`` nodes ``z = relu(...)`` -> ``u = conv(z)`` where u's node is the ONLY consumer of z
     (inside a bottleneck: conv1 -> conv2 -> conv3; between the bottlenecks of a layer: block output -> next block's conv1, whose
@@ -302,19 +265,17 @@ class _ConvBNActFold(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gz, gskip=None):
-        from . import _lib
         x, weight, z, s, mean, var = ctx.saved_tensors
         gz = gz.contiguous()
-        L = _bn_fold_lib()
+        L = _L()
         N, O = gz.shape[0], gz.shape[1]
         HW = gz.numel() // max(N * O, 1)
-        P = _bn_partials.get((N, O, HW))
-        if P is None:
-            P = _bn_partials[(N, O, HW)] = L.kgdet_bn_act_partials(N, O, HW)
+        P = conv1x1._size('kgdet_bn_act_partials', N, O, HW)
         mask = ctx.relu and not (ctx.gate_in is not None and ctx.gate_in.gated)    # (gated: the consumer of z masked gz already)
         need_w, need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         # gz is final (no mask to apply here): no pass over it at all when the weight-gradient kernel can sum its rows
-        sums_in_wgrad = (not mask and GATE_FUSION and (need_w or need_g) and conv1x1.grad_weight_fold_route(x, weight) != 0)
+        route = conv1x1.grad_weight_fold_route(x, weight)
+        sums_in_wgrad = not mask and GATE_FUSION and (need_w or need_g) and route != 0
         g = torch.empty_like(gz) if mask else gz
         st = _lib.raw_stream(gz.device.index)
         partial = None
@@ -332,10 +293,8 @@ class _ConvBNActFold(torch.autograd.Function):
                 ctx.gate_out.gated = True
         gw = sums = None
         if need_w or need_g:      # the split sum of the weight gradient, grad_w = s G and the BatchNorm sums in one launch
-            both = conv1x1.grad_weight_fold(x, weight, g, s, mean, var, ctx.eps, partial, max(P, 1))
-            assert both is not None or partial is not None
-            if both is not None:
-                gw, sums = both
+            if route:
+                gw, sums = conv1x1.grad_weight_fold(x, weight, g, s, mean, var, ctx.eps, partial, max(P, 1))
             else:
                 gw = conv1x1.grad_weight(x, weight, g)
         if sums is None and (need_g or need_b or need_w):
@@ -346,11 +305,6 @@ class _ConvBNActFold(torch.autograd.Function):
         gres = g if (ctx.has_res and ctx.needs_input_grad[7]) else None
         return (gx, gw if need_w else None, sums[1] if need_g else None, sums[0] if need_b else None, None, None, None, gres,
                 None, None, None, None, None)
-
-
-FUSE_STEM = _os.environ.get('KGDET_FUSE_STEM', '1') == '1'   # 0 / False: conv_bn + nn.MaxPool2d (the tests compare the two)
-MERGE_CONV_BN = True    # False: two nodes (conv_split, frozen_bn_act) -- the tests compare the two
-SKIP_ALIAS = _os.environ.get('KGDET_SKIP_ALIAS', '1') == '1'   # identity-branch gradient added inside conv1's grad_input (0: A/B)
 
 
 def _fused_bn_ok(x, bn, residual):
@@ -378,22 +332,18 @@ class _Subsample2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        from . import _lib
         B, C, H, W = x.shape
         y = x.new_empty(B, C, (H + 1) // 2, (W + 1) // 2)
-        _lib.check(_lib.lib().kgdet_subsample2_forward(_lib.ptr(x), _lib.ptr(y), ctypes.c_int64(B * C), ctypes.c_int32(H),
-                                                       ctypes.c_int32(W), _lib.current_stream()), 'subsample2_forward')
+        _lib.check(_L().kgdet_subsample2_forward(x.data_ptr(), y.data_ptr(), B * C, H, W, _lib.raw_stream()), 'subsample2_forward')
         ctx.shape = (B, C, H, W)
         return y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        from . import _lib
         B, C, H, W = ctx.shape
-        gx = gy.new_empty(B, C, H, W)
-        _lib.check(_lib.lib().kgdet_subsample2_backward(_lib.ptr(gy.contiguous()), None, _lib.ptr(gx), ctypes.c_int64(B * C),
-                                                        ctypes.c_int32(H), ctypes.c_int32(W), _lib.current_stream()),
+        gy, gx = gy.contiguous(), gy.new_empty(B, C, H, W)
+        _lib.check(_L().kgdet_subsample2_backward(gy.data_ptr(), None, gx.data_ptr(), B * C, H, W, _lib.raw_stream()),
                    'subsample2_backward')
         return gx
 
@@ -404,8 +354,6 @@ def _subsample2(x):
     return x[:, :, ::2, ::2].contiguous()
 
 
-FUSED_RESIDUAL_1X1 = _os.environ.get('KGDET_INFER_FUSED_RES', '1') == '1'   # conv3 + bn3 + add + ReLU as one kernel where measured faster (0: A/B)
-GEMM_1X1 = _os.environ.get('KGDET_INFER_GEMM_1X1', '1') == '1'     # 0: every inference convolution through MIOpen (A/B)
 _gemm_choice = {}       # (Cin, Cout, B, H, W, residual?, relu) -> True: hipBLASLt GEMM, False: MIOpen convolution
 
 
@@ -430,8 +378,7 @@ _load_gemm_choices()
 def fused_residual_ready(conv3, B, H, W):
     """True when conv3 + bn3 + add + ReLU of this shape runs on the fused kernel (measured choice): the caller may then hand it
     conv2's RAW output and bias (`_conv_bn(..., in_bias=...)`) instead of running conv2's epilogue pass"""
-    return (FUSED_RESIDUAL_1X1 and GEMM_1X1 and
-            _gemm_choice.get((conv3.in_channels, conv3.out_channels, B, H, W, True, True)) == 'fused')
+    return _gemm_choice.get((conv3.in_channels, conv3.out_channels, B, H, W, True, True)) == 'fused'
 
 
 _bias_sums = {}     # (id(bias), id(other)) -> (weakref(bias), weakref(other), bias + other)
@@ -461,15 +408,14 @@ def _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias=None, res_bias=None):
     the choice is MEASURED once per shape during the eager warm-up calls (never while a graph is being captured); returns
     None when the convolution path should run."""
     B, cin, H, W = x.shape
-    cout = hit[1].shape[0]
+    cout = hit.weight.shape[0]
     key = (cin, cout, B, H, W, residual is not None, bool(relu))
     choice = _gemm_choice.get(key)
     if choice is False or (choice is None and torch.cuda.is_current_stream_capturing()):
         return None
-    w2 = hit[1].view(cout, cin)
-    bias16 = hit[5] if len(hit) > 5 else None
+    w2, bias16 = hit.weight.view(cout, cin), hit.bias16
     # res_bias: the residual is the RAW output of the downsample convolution, whose folded bias joins this one's
-    bias32 = _summed_bias(hit[2], res_bias)
+    bias32 = _summed_bias(hit.bias, res_bias)
 
     def gemm():
         x2 = x.permute(0, 2, 3, 1).reshape(-1, cin)
@@ -487,18 +433,15 @@ def _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias=None, res_bias=None):
         # conv3 + bn3 + identity + ReLU as ONE kernel (csrc/conv_nhwc.hip): x, the residual and the output cross the fabric once;
         # with in_bias, x is conv2's RAW output and its bias + ReLU happen as the activations are loaded
         # (residual None: conv1 + bn1 + ReLU, the same kernel without the identity add)
-        from . import _lib
         y = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
-        _lib.check(_lib.lib().kgdet_conv1x1_nhwc_residual_in(
-            _lib.ptr(x), _lib.ptr(in_bias), _lib.ptr(hit[1]), _lib.ptr(bias32), _lib.ptr(residual), _lib.ptr(y),
-            ctypes.c_int64(B * H * W), ctypes.c_int32(cin), ctypes.c_int32(cout), ctypes.c_int32(1 if relu else 0),
-            _lib.current_stream()), 'conv1x1_nhwc_residual')
+        _lib.check(_L().kgdet_conv1x1_nhwc_residual_in(
+            x.data_ptr(), _p(in_bias), hit.weight.data_ptr(), bias32.data_ptr(), _p(residual), y.data_ptr(), B * H * W, cin, cout,
+            1 if relu else 0, _lib.raw_stream()), 'conv1x1_nhwc_residual')
         return y
 
-    ext = NHWC_EXTENDED      # (round 5: no residual, N = 64, K up to 512; 0 = round 4's envelope, A/B)
-    fused_ok = (cin % 16 == 0 and cin <= (512 if ext else 384) and (cout % 128 == 0 or (ext and cout == 64))
-                and (ext or residual is not None)
-                and x.is_contiguous(memory_format=torch.channels_last) and hit[1].is_contiguous(memory_format=torch.channels_last)
+    # (the kernel's envelope since round 5: with or without a residual, N = 64 or a multiple of 128, K up to 512)
+    fused_ok = (cin % 16 == 0 and cin <= 512 and (cout % 128 == 0 or cout == 64)
+                and x.is_contiguous(memory_format=torch.channels_last) and hit.weight.is_contiguous(memory_format=torch.channels_last)
                 and (residual is None or (residual.is_contiguous(memory_format=torch.channels_last)
                                           and residual.shape == (B, cout, H, W))))
     if choice == 'fused' and fused_ok:   # the choice is keyed by shape; layout / contiguity are properties of THIS call
@@ -509,7 +452,7 @@ def _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias=None, res_bias=None):
         return gemm()
     if choice is None:
         def conv_path():
-            y = F.conv2d(x, hit[1], None, conv.stride, conv.padding, conv.dilation, conv.groups)
+            y = F.conv2d(x, hit.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
             return _epilogue_(y, bias32, residual, relu)
 
         def timed(fn):
@@ -523,7 +466,7 @@ def _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias=None, res_bias=None):
             e1.synchronize()
             return e0.elapsed_time(e1)
         t_conv, t_gemm = timed(conv_path), timed(gemm)
-        t_fused = timed(fused) if (fused_ok and FUSED_RESIDUAL_1X1) else float('inf')
+        t_fused = timed(fused) if fused_ok else float('inf')
         if t_fused < 0.95 * min(t_conv, t_gemm):
             choice = 'fused'
         else:
@@ -534,6 +477,27 @@ def _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias=None, res_bias=None):
         if not choice:
             return None
     return gemm()
+
+
+def _merged_node(conv, bn, x, relu, residual, skip=False, gate_in=None, gate_out=None, folded_only=False):
+    """The ONE training node of ``[relu](bn(conv(x)) [+ residual])`` for an x that ``conv1x1.applicable`` accepted: _ConvBNActFold
+    from the pair's second step on, _ConvBNAct before (``folded_only``: None then); with ``skip`` the (output, x or its alias)
+    pair.  None: the caller runs the convolution and the BatchNorm as two nodes."""
+    w = conv.weight
+    if not (MERGE_CONV_BN and _fused_bn_ok(x, bn, residual) and x.shape[0] * w.shape[0] <= 65535
+            and (residual is None or residual.shape[1] == w.shape[0])):
+        return None
+    alias = skip and x.requires_grad     # the identity branch's gradient arrives at the node and is added inside grad_input
+    args = (x, w, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, residual, relu, alias)
+    fold = conv1x1.fold_images(w, bn) if bn.affine else None
+    if fold is not None:
+        # (skip without the alias: x has a second consumer, the identity branch -- its gradient must not be gated)
+        out = _ConvBNActFold.apply(*args, fold, gate_in, None if (skip and not alias) else gate_out)
+    elif folded_only:
+        return None
+    else:
+        out = _ConvBNAct.apply(*args)
+    return (out, x) if (skip and not alias) else out
 
 
 def conv_bn(conv, bn, x, relu=False, residual=None, skip=False, gate_in=None, gate_out=None):
@@ -563,24 +527,10 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
         return F.relu(out, inplace=True) if relu else out
     if torch.is_grad_enabled():
         if conv1x1.applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups):
-            if (MERGE_CONV_BN and _fused_bn_ok(x, bn, residual) and x.shape[0] * conv.weight.shape[0] <= 65535
-                    and (residual is None or residual.shape[1] == conv.weight.shape[0])):
-                fold = conv1x1.fold_images(conv.weight, bn) if bn.affine else None
-                if fold is not None:     # from the pair's second step on: BatchNorm folded into the convolution
-                    if skip and SKIP_ALIAS and x.requires_grad:
-                        return _ConvBNActFold.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                                    bn.eps, residual, relu, True, fold, gate_in, gate_out)
-                    # (skip without the alias: x has a second consumer, the identity branch -- its gradient must not be gated)
-                    out = _ConvBNActFold.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                               residual, relu, False, fold, gate_in, None if skip else gate_out)
-                    return (out, x) if skip else out
-                if skip and SKIP_ALIAS and x.requires_grad:
-                    return _ConvBNAct.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                            residual, relu, True)
-                out = _ConvBNAct.apply(x, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                       residual, relu)
-                return (out, x) if skip else out
-            return frozen_bn_act(conv1x1.conv_split(x, conv.weight), bn, residual, relu)   # split-bf16 MFMA GEMMs
+            out = _merged_node(conv, bn, x, relu, residual, skip, gate_in, gate_out)
+            if out is None:
+                out = frozen_bn_act(conv1x1.conv_split(x, conv.weight), bn, residual, relu)   # split-bf16 MFMA GEMMs
+            return out
         if conv1x1.applicable_stride2(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups):
             return frozen_bn_act(conv1x1.conv3x3_stride2(x, conv.weight), bn, residual, relu)
         if (conv.kernel_size == (1, 1) and conv.stride == (2, 2) and conv.padding == (0, 0) and x.is_cuda
@@ -589,13 +539,10 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
             # kernels run at 13-18 TFLOP/s backward; the quarter-size copy + the split-bf16 GEMMs are ~2x faster
             xs = _subsample2(x)
             if conv1x1.applicable(xs, conv.weight):
-                fold = (conv1x1.fold_images(conv.weight, bn)
-                        if (MERGE_CONV_BN and bn.affine and _fused_bn_ok(xs, bn, residual)
-                            and xs.shape[0] * conv.weight.shape[0] <= 65535) else None)
-                if fold is not None:
-                    return _ConvBNActFold.apply(xs, conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps,
-                                                residual, relu, False, fold)
-                return frozen_bn_act(conv1x1.conv_split(xs, conv.weight), bn, residual, relu)
+                out = _merged_node(conv, bn, xs, relu, residual, folded_only=True)
+                if out is None:
+                    out = frozen_bn_act(conv1x1.conv_split(xs, conv.weight), bn, residual, relu)
+                return out
         return frozen_bn_act(conv(x), bn, residual, relu)
     bf16 = x.is_cuda and (x.dtype == torch.bfloat16 or (torch.is_autocast_enabled()
                                                         and torch.get_autocast_dtype('cuda') == torch.bfloat16))
@@ -603,7 +550,7 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
     # staleness: in-place updates (load_state_dict's copy_, optimizer steps that bump the counter) change _version
     ver = (conv.weight._version, bn.running_mean._version, bn.running_var._version,
            bn.weight._version if bn.affine else 0, bn.bias._version if bn.affine else 0)
-    if hit is None or hit[0]() is not conv or hit[4] != ver:
+    if hit is None or hit.conv() is not conv or hit.version != ver:
         scale = bn.weight * torch.rsqrt(bn.running_var + bn.eps) if bn.affine else torch.rsqrt(bn.running_var + bn.eps)
         shift = (bn.bias if bn.affine else 0) - bn.running_mean * scale
         w = (conv.weight * scale.view(-1, 1, 1, 1)).detach()
@@ -612,28 +559,29 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
         packed = None
         if not bf16 and conv1x1.applicable(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
             packed = conv1x1._pack(w.contiguous(), False)     # fp32 inference: split-bf16 MFMA kernels, packed once
-        hit = (weakref.ref(conv), w, shift.detach().float().contiguous(), packed, ver,
-               shift.detach().to(torch.bfloat16).contiguous() if bf16 else None)
+        hit = _Folded(weakref.ref(conv), w, shift.detach().float().contiguous(), packed, ver,
+                      shift.detach().to(torch.bfloat16).contiguous() if bf16 else None)
         _fold_cache[(id(conv), bf16)] = hit
     if bf16 and not x.is_contiguous(memory_format=torch.channels_last):
         x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-    if (bf16 and GEMM_1X1 and not raw and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
+    if (bf16 and not raw and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0)
             and conv.groups == 1 and x.dtype == torch.bfloat16 and (residual is None or residual.dtype == torch.bfloat16)):
         out = _conv1x1_as_gemm(conv, hit, x, residual, relu, in_bias, res_bias)
         if out is not None:
             return out
     if in_bias is not None:      # the convolution route after all: conv2's epilogue as its own pass
         x = _epilogue_(x, in_bias, None, True)
-    bias = _summed_bias(hit[2], res_bias)     # (res_bias: `residual` is a RAW convolution output whose bias is added here)
-    if hit[3] is not None and x.dtype == torch.float32 and x.is_contiguous() and x.shape[2] * x.shape[3] % 2 == 0:
-        if _FUSE_EPI and (residual is None or (residual.dtype == torch.float32 and residual.is_contiguous())):
+    bias = _summed_bias(hit.bias, res_bias)     # (res_bias: `residual` is a RAW convolution output whose bias is added here)
+    taps = hit.weight.shape[2] * hit.weight.shape[3]
+    if hit.packed is not None and x.dtype == torch.float32 and x.is_contiguous() and x.shape[2] * x.shape[3] % 2 == 0:
+        if residual is None or (residual.dtype == torch.float32 and residual.is_contiguous()):
             # bias, residual and ReLU ride on the convolution's store: no separate epilogue pass
-            return conv1x1._apply(hit[3], x, hit[1].shape[0], hit[1].shape[2] * hit[1].shape[3], 1, bias, residual, relu)
-        out = conv1x1._apply(hit[3], x, hit[1].shape[0], hit[1].shape[2] * hit[1].shape[3])
+            return conv1x1._apply(hit.packed, x, hit.weight.shape[0], taps, 1, bias, residual, relu)
+        out = conv1x1._apply(hit.packed, x, hit.weight.shape[0], taps)
     else:
-        out = F.conv2d(x, hit[1], None, conv.stride, conv.padding, conv.dilation, conv.groups)
+        out = F.conv2d(x, hit.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     if raw:     # (the stem: the caller fuses bias + ReLU with the pooling)
-        return out, hit[2]
+        return out, hit.bias
     return _epilogue_(out, bias, residual, relu)
 
 
@@ -874,12 +822,11 @@ class ResNet(nn.Module):
                                                       or (bn.affine and (bn.weight.requires_grad or bn.bias.requires_grad))))
                 and (mp.kernel_size, mp.stride, mp.padding, mp.dilation, mp.ceil_mode) == (3, 2, 1, 1, False)
                 and x.shape[0] * self.conv1.out_channels <= 65535):
-            from . import _lib
             with torch.no_grad():
                 y = _stem_conv(self.conv1, x)
                 N, C, H, W = y.shape
                 out = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=y.dtype, device=y.device)
-                _lib.check(_bn_lib().kgdet_bn_relu_maxpool(
+                _lib.check(_L().kgdet_bn_relu_maxpool(
                     _p(y), _p(bn.weight), _p(bn.bias), _p(bn.running_mean), _p(bn.running_var), bn.eps, _p(out), N, C, H, W,
                     _lib.raw_stream(y.device.index)), 'bn_relu_maxpool')
             return out
@@ -891,14 +838,12 @@ class ResNet(nn.Module):
             C = y.shape[1]
             if (y.dtype in (torch.float32, torch.bfloat16) and y.dim() == 4 and not y.is_contiguous()
                     and y.is_contiguous(memory_format=torch.channels_last) and C % (4 if y.dtype == torch.float32 else 8) == 0):
-                from . import _lib
                 N, _, H, W = y.shape
                 out = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=y.dtype, device=y.device,
                                   memory_format=torch.channels_last)
-                _lib.check(_lib.lib().kgdet_bias_relu_maxpool_nhwc(
-                    _lib.ptr(y), _lib.ptr(shift), _lib.ptr(out), ctypes.c_int64(N), ctypes.c_int32(C), ctypes.c_int32(H),
-                    ctypes.c_int32(W), ctypes.c_int32(0 if y.dtype == torch.float32 else 1), _lib.current_stream()),
-                    'bias_relu_maxpool_nhwc')
+                _lib.check(_L().kgdet_bias_relu_maxpool_nhwc(y.data_ptr(), shift.data_ptr(), out.data_ptr(), N, C, H, W,
+                                                             0 if y.dtype == torch.float32 else 1, _lib.raw_stream()),
+                           'bias_relu_maxpool_nhwc')
                 return out
             return self.maxpool(_epilogue_(y, shift, None, True))
         return self.maxpool(conv_bn(self.conv1, self.norm1, x, relu=True))

@@ -4,7 +4,9 @@
 ``conv_split(x, weight)`` equals ``F.conv2d(x, weight, padding=k // 2)`` for a ``[O, C, k, k]`` weight, k in {1, 3},
 to fp32-level accuracy (~5e-6 of the output scale), forward and both gradients; used by the backbone's bottlenecks
 (kgdet_amd/backbone.py), where MIOpen's fp32 kernels run at 60-110 TFLOP/s."""
+import collections
 import ctypes
+import os as _os
 import weakref
 
 import torch
@@ -12,73 +14,79 @@ import torch
 from . import _lib
 
 
-# The 3x3 grad_weight kernel (conv_nt8<9>): 95-104 us for the layer-2 / layer-3 shapes against MIOpen's implicit-GEMM
-# wrw at 110 us + its layout transposes and output zeroing (~175 us in the step profile).  KGDET_SPLIT_WGRAD3=0 and
-# KGDET_PACK_BOTH=0 switch back for A/B measurements.
-import os as _os
-SPLIT_GRAD_WEIGHT_3X3 = _os.environ.get('KGDET_SPLIT_WGRAD3', '1') == '1'
-PACK_BOTH = _os.environ.get('KGDET_PACK_BOTH', '1') == '1'
-
-
-PAD_GRAD_WEIGHT_3X3 = _os.environ.get('KGDET_NO_WPAD') is None   # (A/B switch for the zero-padded odd-width route)
-# Maps with an odd pixel count (13 x 21, 7 x 11: the two coarsest levels of a five-level head) go to the split kernels as they
-# are (round 4: tools/check_odd_maps.py -- forward 3e-7, gradients 5e-6 of torch's float64 convolution; 16-byte loads need 4-byte
-# alignment only on gfx950).  0: rounds 2-3's route, one zero column appended and cut off around every convolution (pad_odd /
-# unpad_odd below: six extra launches per convolution and step, ~130 of a config-5 step)
-DIRECT_ODD_MAPS = _os.environ.get('KGDET_DIRECT_ODD_MAPS', '1') == '1'
+# ---- switches (the other setting of each, and who uses it) ----------------------------------------------------------------
 ENABLED = True      # False: every dense convolution stays on MIOpen's fp32 kernels (dcn.arithmetic('exact'))
-
-
-# 1x1 convolutions of ANY channel counts (round 6: the head's 13- / 588- / 166-channel output convolutions): the operand images pad
-# a reduction that ends inside a 16-channel chunk with zeros, the kernel re-reads the last channel for them.  0: those stay with
-# the vendor libraries (A/B).
-RAGGED_1X1 = _os.environ.get('KGDET_CONV_RAGGED_1X1', '1') == '1'
+# 0: bf16 parts in the FORWARD operand images too, round 2's arithmetic (the numerics tests, tools/chk_head_f16.py).  Default: two
+# fp16 parts (22 mantissa bits, fp32-class results; csrc/dense_common.h split_pair_t).  The packed tensor carries the format as
+# an attribute (`kgdet_f16`), `_apply` reads it; transposed (grad_input) images and the weight-gradient kernels stay bf16:
+# gradients need the exponent range.
+FORWARD_F16 = _os.environ.get('KGDET_CONV_FWD_F16', '1') == '1'
+SPLIT_GRAD_WEIGHT_3X3 = True      # False: MIOpen's weight gradient for every 3x3 convolution (the fp64 convolution test pins it on)
+# 0: frozen BatchNorms stay their own pass behind the convolution (test_folded_batchnorm_step_equals_the_unfolded_step)
+FOLD_BN = _os.environ.get('KGDET_FOLD_BN', '1') == '1'
 
 
 def applicable(x, weight, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1):
+    """stride-1 convolutions the split kernels take: 3x3 with channel counts in multiples of 16, 1x1 with ANY channel counts whose
+    product is even (the head's 13- / 588- / 166-channel outputs: the operand images pad a reduction that ends inside a
+    16-channel chunk with zeros), on maps of four pixels or more -- odd pixel counts (13 x 21, 7 x 11) in place: 16-byte loads
+    need 4-byte alignment only on gfx950 (tools/check_odd_maps.py)"""
     k = weight.shape[2]
     aligned = weight.shape[1] % 16 == 0 and weight.shape[0] % 16 == 0
     return (ENABLED and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4
             and weight.shape[2] == weight.shape[3] and k in (1, 3) and tuple(stride) == (1, 1)
             and tuple(padding) == (k // 2, k // 2) and tuple(dilation) == (1, 1) and groups == 1
-            and x.is_contiguous() and (aligned or (k == 1 and RAGGED_1X1 and (weight.shape[0] * weight.shape[1]) % 2 == 0))
-            and ((x.shape[2] * x.shape[3]) % 2 == 0 or DIRECT_ODD_MAPS) and x.shape[2] * x.shape[3] >= 4
-            and not torch.is_autocast_enabled())
+            and x.is_contiguous() and (aligned or (k == 1 and (weight.shape[0] * weight.shape[1]) % 2 == 0))
+            and x.shape[2] * x.shape[3] >= 4 and not torch.is_autocast_enabled())
 
 
+# ---- the library's entry points that this module and backbone.py call (include/kgdet_hip.h), declared once: with argtypes the
+# calls pass plain Python ints, `data_ptr()` and None, which marshal ~3x faster than c_int / c_void_p objects
+_vp, _i32, _i64, _sz, _f32, _int = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float,
+                                    ctypes.c_int)
+_FOLD_TAIL = [_vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp]      # w, s, mean, var, eps, bn_partial, P, grad_beta, grad_gamma
+_PROTOTYPES = (
+    ('kgdet_conv_packed_bytes', _sz, [_i32, _i32, _i32]),
+    ('kgdet_conv_apply_workspace_bytes', _sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    ('kgdet_conv_pack_fmt', _int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
+    ('kgdet_conv_pack_both_fmt', _int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
+    ('kgdet_conv_pack_blocks', _i64, [_i32, _i32, _i32]),
+    ('kgdet_conv_pack_multi', _int, [_vp, _i32, _i64, _vp]),
+    ('kgdet_conv_apply_gated_fmt', _int,
+     [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    ('kgdet_conv3x3_s2_grad_input', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    ('kgdet_conv1x1_grad_weight_workspace_bytes', _sz, [_i64, _i32, _i32, _i64]),
+    ('kgdet_conv3x3_grad_weight_workspace_bytes', _sz, [_i64, _i32, _i32, _i32, _i32]),
+    ('kgdet_conv3x3_s2_grad_weight_workspace_bytes', _sz, [_i64, _i32, _i32, _i32, _i32]),
+    ('kgdet_conv1x1_grad_weight', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _sz, _vp]),
+    ('kgdet_conv3x3_grad_weight', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    ('kgdet_conv3x3_s2_grad_weight', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    ('kgdet_conv1x1_grad_weight_fold', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _sz] + _FOLD_TAIL + [_vp]),
+    ('kgdet_conv3x3_grad_weight_fold', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz] + _FOLD_TAIL + [_vp]),
+    # backbone.py
+    ('kgdet_stem_conv7x7_s2_fmt', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    ('kgdet_bias_act', _int, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp]),
+    ('kgdet_bias_relu_maxpool_nhwc', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
+    ('kgdet_conv1x1_nhwc_residual_in', _int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
+    ('kgdet_subsample2_forward', _int, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    ('kgdet_subsample2_backward', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
+    ('kgdet_bn_act_partials', _i32, [_i64, _i32, _i64]),
+    ('kgdet_bn_act_forward', _int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
+    ('kgdet_bn_act_backward', _int,
+     [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _i64, _vp]),
+    ('kgdet_bn_relu_maxpool', _int, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _vp]),
+    ('kgdet_bn_fold_backward', _int, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _i64, _vp]),
+    ('kgdet_bn_fold_finish', _int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _vp]))
 _L = None
-_sizes = {}     # (query, args) -> bytes: the workspace / image sizes depend on the shape only
+_sizes = {}     # (query, args) -> its answer: workspace / image sizes and partial counts depend on the shape only
 
 
-def _lib_sizes():
-    """the library with argtypes declared once (plain Python ints / pointers marshal ~3x faster than c_int objects)"""
+def _library():
+    """the loaded library with every prototype of the table declared"""
     global _L
     if _L is None:
         L = _lib.lib()
-        vp, i32, i64, sz = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t
-        for name, res, args in (
-                ('kgdet_conv_packed_bytes', sz, [i32, i32, i32]),
-                ('kgdet_conv_apply_workspace_bytes', sz, [i64, i32, i32, i32, i32, i32, i32]),
-                ('kgdet_conv1x1_grad_weight_workspace_bytes', sz, [i64, i32, i32, i64]),
-                ('kgdet_conv3x3_grad_weight_workspace_bytes', sz, [i64, i32, i32, i32, i32]),
-                ('kgdet_conv_pack_fmt', ctypes.c_int, [vp, i32, i32, i32, i32, vp, i32, vp]),
-                ('kgdet_conv_pack_both_fmt', ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, vp]),
-                ('kgdet_conv_pack_blocks', i64, [i32, i32, i32]),
-                ('kgdet_conv_pack_multi', ctypes.c_int, [vp, i32, i64, vp]),
-                ('kgdet_conv_apply', ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
-                ('kgdet_conv_apply_epilogue_fmt', ctypes.c_int,
-                 [vp, vp, vp, vp, vp, i32, i64, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
-                ('kgdet_conv_apply_gated_fmt', ctypes.c_int,
-                 [vp, vp, vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]),
-                ('kgdet_conv3x3_s2_grad_input', ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, vp]),
-                ('kgdet_conv3x3_s2_grad_weight_workspace_bytes', sz, [i64, i32, i32, i32, i32]),
-                ('kgdet_conv3x3_s2_grad_weight', ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, vp, sz, vp]),
-                ('kgdet_conv1x1_grad_weight', ctypes.c_int, [vp, vp, vp, i64, i32, i32, i64, vp, sz, vp]),
-                ('kgdet_conv1x1_grad_weight_fold', ctypes.c_int,
-                 [vp, vp, vp, i64, i32, i32, i64, vp, sz, vp, vp, vp, vp, ctypes.c_float, vp, i32, vp, vp, vp]),
-                ('kgdet_conv3x3_grad_weight_fold', ctypes.c_int,
-                 [vp, vp, vp, i64, i32, i32, i32, i32, vp, sz, vp, vp, vp, vp, ctypes.c_float, vp, i32, vp, vp, vp]),
-                ('kgdet_conv3x3_grad_weight', ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, i32, vp, sz, vp])):
+        for name, res, args in _PROTOTYPES:
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _L = L
@@ -89,19 +97,12 @@ def _size(name, *args):
     key = (name, args)
     n = _sizes.get(key)
     if n is None:
-        n = _sizes[key] = getattr(_lib_sizes(), name)(*args)
+        n = _sizes[key] = getattr(_library(), name)(*args)
     return n
 
 
 def _stream():
     return _lib.raw_stream()
-
-
-# Operand format of the FORWARD images (activations x weights): two fp16 parts (22 mantissa bits, fp32-class results) instead of
-# two bf16 parts (16 bits) -- csrc/dense_common.h split_pair_t.  The packed tensor carries the format as an attribute
-# (`kgdet_f16`), `_apply` reads it; transposed (grad_input) images and the weight-gradient kernels stay bf16: gradients need
-# the exponent range.  KGDET_CONV_FWD_F16=0: bf16 parts everywhere (A/B, and round 2's arithmetic).
-FORWARD_F16 = _os.environ.get('KGDET_CONV_FWD_F16', '1') == '1'
 
 
 def _mark(img, f16):
@@ -111,7 +112,7 @@ def _mark(img, f16):
 
 def _pack(weight, transpose):
     """weight [O, C, k, k] -> operand image (forward: rows O; transpose: rows C with mirrored taps)"""
-    L = _lib_sizes()
+    L = _library()
     O, C, taps = weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3]
     M, K = (C, O) if transpose else (O, C)
     img = torch.empty(_size('kgdet_conv_packed_bytes', M, K, taps), dtype=torch.uint8, device=weight.device)
@@ -123,7 +124,7 @@ def _pack(weight, transpose):
 
 def _pack_both(weight):
     """forward and grad_input images of one weight in one launch"""
-    L = _lib_sizes()
+    L = _library()
     O, C, taps = weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3]
     img = torch.empty(_size('kgdet_conv_packed_bytes', O, C, taps), dtype=torch.uint8, device=weight.device)
     img_t = torch.empty(_size('kgdet_conv_packed_bytes', C, O, taps), dtype=torch.uint8, device=weight.device)
@@ -135,7 +136,7 @@ def _pack_both(weight):
 def _apply(img, x, M, taps, stride=1, bias=None, residual=None, relu=False, gate=None):
     """y = conv(x) through the packed image; inference epilogue [relu](y + bias [+ residual]) fused into the store;
     ``gate`` (shape of y): y is zeroed where gate <= 0 (kgdet_conv_apply_gated_fmt: a ReLU's backward in the store)"""
-    L = _lib_sizes()
+    L = _library()
     B, K, H, W = x.shape
     y = torch.empty((B, M, (H + stride - 1) // stride, (W + stride - 1) // stride), dtype=torch.float32, device=x.device)
     nbytes = _size('kgdet_conv_apply_workspace_bytes', B, M, K, H, W, taps, stride)
@@ -168,22 +169,21 @@ _entries = {}        # id(weight) -> _Entry
 _token = 0           # current scope generation; 0 = no scope active
 _generation = 0
 _table = None        # (key, device descriptor tensor, total blocks)
-PACK_MULTI = _os.environ.get('KGDET_PACK_MULTI', '1') == '1'
 
 
 # ---- frozen-statistics BatchNorm folded into the convolution in front of it (kgdet_amd/backbone.py _ConvBNActFold) ------
 # A (weight, BatchNorm) pair seen inside a step scope joins `_fold_entries`; from the next scope on the scope's pack launch
 # writes the images of w * s, s = gamma / sqrt(var + eps), and the pair's s and t = beta - mean * s are refreshed before it by a
 # handful of multi-tensor torch ops over flat buffers (the parameters change every step).
-FOLD_BN = _os.environ.get('KGDET_FOLD_BN', '1') == '1'
-
-
 class _FoldEntry(object):
     __slots__ = ('ref', 'bn', 'img', 'img_t', 's', 't', 'token', 'ptr')
 
 
 _fold_entries = {}   # id(weight) -> _FoldEntry
-_fold_flat = None    # (key, S, T, TMP, EPS, s views, t views, tmp views, gammas, betas, means, vars)
+# the flat buffers of s, t, a temporary and eps over all folded pairs, their per-pair slices and the BatchNorm tensors they are
+# refreshed from.  Training state, not an inference cache: a captured training graph writes TMP and EPS through raw pointers
+_FoldFlat = collections.namedtuple('_FoldFlat', 'key S T TMP EPS s t tmp gammas betas means vars')
+_fold_flat = None
 
 
 def _fold_refresh(live):
@@ -193,7 +193,7 @@ def _fold_refresh(live):
     #  load_state_dict(assign=True), must not leave the old tensors' values in the folded images)
     key = tuple((k, e.ptr, id(e.bn()), id(e.bn().weight), id(e.bn().bias), id(e.bn().running_mean), id(e.bn().running_var),
                  e.bn().weight.data_ptr(), e.bn().running_var.data_ptr()) for k, e in live)
-    if _fold_flat is None or _fold_flat[0] != key:
+    if _fold_flat is None or _fold_flat.key != key:
         dev = live[0][1].img.device
         sizes = [e.ref().shape[0] for _, e in live]
         total = sum(sizes)
@@ -205,17 +205,17 @@ def _fold_refresh(live):
             e.s, e.t = sv[-1], tv[-1]
             off += n
         bns = [e.bn() for _, e in live]
-        _fold_flat = (key, S, T, TMP, EPS, sv, tv, mv, [b.weight for b in bns], [b.bias for b in bns],
-                      [b.running_mean for b in bns], [b.running_var for b in bns])
-    _, S, T, TMP, EPS, sv, tv, mv, gammas, betas, means, vars_ = _fold_flat
+        _fold_flat = _FoldFlat(key, S, T, TMP, EPS, sv, tv, mv, [b.weight for b in bns], [b.bias for b in bns],
+                               [b.running_mean for b in bns], [b.running_var for b in bns])
+    f = _fold_flat
     with torch.no_grad():
-        torch._foreach_copy_(mv, vars_)
-        TMP.add_(EPS).rsqrt_()                        # 1 / sqrt(var + eps)
-        torch._foreach_copy_(sv, gammas)
-        S.mul_(TMP)                                   # s = gamma * invstd
-        torch._foreach_copy_(tv, means)
-        T.mul_(S).neg_()
-        torch._foreach_add_(tv, betas)                # t = beta - mean * s
+        torch._foreach_copy_(f.tmp, f.vars)
+        f.TMP.add_(f.EPS).rsqrt_()                    # 1 / sqrt(var + eps)
+        torch._foreach_copy_(f.s, f.gammas)
+        f.S.mul_(f.TMP)                               # s = gamma * invstd
+        torch._foreach_copy_(f.t, f.means)
+        f.T.mul_(f.S).neg_()
+        torch._foreach_add_(f.t, f.betas)             # t = beta - mean * s
 
 
 def _launch_multi():
@@ -237,7 +237,7 @@ def _launch_multi():
     # the rows hold raw device pointers: the key names them too (ids alone are reused by CPython once a model is freed)
     key = (tuple((k, e.ptr, e.img.data_ptr(), e.img_t.data_ptr()) for k, e in live),
            tuple((k, e.ptr, e.img.data_ptr(), e.img_t.data_ptr(), e.s.data_ptr()) for k, e in folded))
-    L = _lib_sizes()
+    L = _library()
     if _table is None or _table[0] != key:
         rows, first = [], 0
         for _, e in live + folded:
@@ -258,7 +258,7 @@ def _launch_multi():
 def fold_images(weight, bn):
     """(forward image, grad_input image, s, t) of conv(., weight) followed by the frozen-statistics BatchNorm ``bn``, packed by
     the current step scope's launch -- or None: outside a scope, or the pair is new (it joins the set for the next scope)"""
-    if not (FOLD_BN and PACK_MULTI and _token):
+    if not (FOLD_BN and _token):
         return None
     e = _fold_entries.get(id(weight))
     if e is not None and e.ref() is weight and e.ptr == weight.data_ptr() and e.bn() is bn:
@@ -285,7 +285,7 @@ class step_scope(object):
         self.prev = _token
         _generation += 1
         _token = _generation
-        if PACK_MULTI and (_entries or _fold_entries):
+        if _entries or _fold_entries:
             _launch_multi()
 
     def __exit__(self, *exc):
@@ -305,20 +305,19 @@ def alias(proxy, param):
 
 def forward_images(x, weight):
     """(forward operand image, grad_input operand image or None) of a contiguous weight"""
-    both = PACK_BOTH and x.requires_grad and (weight.shape[0] % 16 == 0 or weight.shape[2] == 1)
+    both = x.requires_grad and (weight.shape[0] % 16 == 0 or weight.shape[2] == 1)
     a = _aliases.get(id(weight))
     if a is not None and a[0]() is weight:
         origin = a[1]()
         if origin is not None and origin.data_ptr() == weight.data_ptr() and origin.shape == weight.shape:
             weight = origin      # (same storage: the images are the parameter's)
-    if both and PACK_MULTI and _token:
+    if both and _token:
         e = _entries.get(id(weight))
         if e is not None and e.ref() is weight and e.ptr == weight.data_ptr():
             if e.token != _token:       # joined the set after this scope's pack launch
-                _lib.check(_lib_sizes().kgdet_conv_pack_both_fmt(weight.data_ptr(), weight.shape[0], weight.shape[1],
-                                                                 weight.shape[2] * weight.shape[3], e.img.data_ptr(),
-                                                                 e.img_t.data_ptr(), 1 if getattr(e.img, 'kgdet_f16', False) else 0,
-                                                                 _stream()), 'conv_pack_both')
+                _lib.check(_library().kgdet_conv_pack_both_fmt(
+                    weight.data_ptr(), weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3], e.img.data_ptr(),
+                    e.img_t.data_ptr(), 1 if getattr(e.img, 'kgdet_f16', False) else 0, _stream()), 'conv_pack_both')
                 e.token = _token
             return e.img, e.img_t
         img, img_t = _pack_both(weight)
@@ -332,80 +331,50 @@ def forward_images(x, weight):
     return _pack(weight, False), None
 
 
-def grad_weight(x, weight, gy):
-    """grad of ``conv(x, weight)`` (stride 1, padding k // 2) with respect to the weight"""
-    O, C, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    L = _lib_sizes()
+def grad_weight_fold_route(x, weight):
+    """3 / 1: the weight gradient of a stride-1 convolution runs on the 3x3 / 1x1 split kernel (any map: for rows that are no
+    multiple of 4 floats, the 25 x 42 head / FPN maps, the library pads both operands inside its workspace -- 42 against the
+    76 us of MIOpen's fp32 Winograd weight gradient, and deterministic); 0: on MIOpen (3x3 with C % 128 != 0)"""
+    C, k = weight.shape[1], weight.shape[2]
     if k == 3 and SPLIT_GRAD_WEIGHT_3X3 and C % 128 == 0:
-        if x.shape[3] % 4 and not PAD_GRAD_WEIGHT_3X3:
-            return torch.nn.grad.conv2d_weight(x, weight.shape, gy, padding=1)
-        # (W % 4 != 0, the 25 x 42 head / FPN maps: the library pads both operands inside its workspace, one launch --
-        # the split kernel beats MIOpen's fp32 Winograd weight gradient, 42 against 76 us per call, and is deterministic)
-        B, H, W = x.shape[0], x.shape[2], x.shape[3]
-        nbytes = _size('kgdet_conv3x3_grad_weight_workspace_bytes', B, O, C, H, W)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        gw = torch.empty_like(weight)
-        _lib.check(L.kgdet_conv3x3_grad_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, H, W,
-                                               ws.data_ptr(), nbytes, _stream()), 'conv3x3_grad_weight')
-        return gw
-    if k != 1 or ((x.shape[2] * x.shape[3]) % 4 != 0 and not PAD_GRAD_WEIGHT_3X3):
-        # other 3x3 shapes: MIOpen.  (1x1 on maps with H*W % 4 != 0, e.g. 25 x 42: the library pads both operands)
-        return torch.nn.grad.conv2d_weight(x, weight.shape, gy, padding=k // 2)
-    B, HW = x.shape[0], x.shape[2] * x.shape[3]
-    nbytes = _size('kgdet_conv1x1_grad_weight_workspace_bytes', B, O, C, HW)
+        return 3
+    return 1 if k == 1 else 0
+
+
+def _grad_weight_launch(name, x, weight, gy, fold=()):
+    """size query, workspace, output, launch, check of the weight-gradient entry point ``name`` (``fold``: the arguments of its
+    _fold variant between the workspace and the stream) -> grad_weight"""
+    B, O, C = x.shape[0], weight.shape[0], weight.shape[1]
+    dims = (x.shape[2] * x.shape[3],) if name == 'kgdet_conv1x1_grad_weight' else (x.shape[2], x.shape[3])
+    nbytes = _size(name + '_workspace_bytes', B, O, C, *dims)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     gw = torch.empty_like(weight)
-    _lib.check(L.kgdet_conv1x1_grad_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, HW,
-                                           ws.data_ptr(), nbytes, _stream()), 'conv1x1_grad_weight')
+    launch = getattr(_library(), name + '_fold' if fold else name)
+    _lib.check(launch(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, *dims, ws.data_ptr(), nbytes, *fold, _stream()), name)
     return gw
 
 
-def grad_weight_fold_route(x, weight):
-    """3 / 1: grad_weight_fold serves this problem with the 3x3 / 1x1 split kernels; 0: it returns None"""
-    C, k = weight.shape[1], weight.shape[2]
-    if k == 3 and SPLIT_GRAD_WEIGHT_3X3 and C % 128 == 0 and (x.shape[3] % 4 == 0 or PAD_GRAD_WEIGHT_3X3):
-        return 3
-    if k == 1 and ((x.shape[2] * x.shape[3]) % 4 == 0 or PAD_GRAD_WEIGHT_3X3):
-        return 1
-    return 0
+def grad_weight(x, weight, gy):
+    """grad of ``conv(x, weight)`` (stride 1, padding k // 2) with respect to the weight"""
+    route = grad_weight_fold_route(x, weight)
+    if not route:
+        return torch.nn.grad.conv2d_weight(x, weight.shape, gy, padding=weight.shape[2] // 2)
+    return _grad_weight_launch('kgdet_conv%dx%d_grad_weight' % (route, route), x, weight, gy)
 
 
 def grad_weight_fold(x, weight, gy, s, mean, var, eps, bn_partial, P, want_gamma=True):
     """grad_weight of a convolution with a folded BatchNorm (backbone._ConvBNActFold): (s * G, sums [2, O] = grad_beta,
-    grad_gamma) from ONE launch behind the split kernel -- or None where grad_weight would take another route.
-    ``bn_partial=None`` (P = 0): the per-channel sums of gy are formed inside the weight-gradient kernel."""
-    O, C, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    L = _lib_sizes()
-    if bn_partial is None:
-        P = 0
-
-        class bn_partial(object):        # (a null pointer for the two calls below)
-            @staticmethod
-            def data_ptr():
-                return None
-    if k == 3 and SPLIT_GRAD_WEIGHT_3X3 and C % 128 == 0 and (x.shape[3] % 4 == 0 or PAD_GRAD_WEIGHT_3X3):
-        B, H, W = x.shape[0], x.shape[2], x.shape[3]
-        nbytes = _size('kgdet_conv3x3_grad_weight_workspace_bytes', B, O, C, H, W)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        gw = torch.empty_like(weight)
-        sums = torch.empty((2, O), dtype=torch.float32, device=x.device)
-        _lib.check(L.kgdet_conv3x3_grad_weight_fold(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, H, W, ws.data_ptr(), nbytes,
-                                                    weight.data_ptr(), s.data_ptr(), mean.data_ptr(), var.data_ptr(), eps,
-                                                    bn_partial.data_ptr(), P, sums[0].data_ptr(),
-                                                    sums[1].data_ptr() if want_gamma else None, _stream()), 'conv3x3_grad_weight_fold')
-        return gw, sums
-    if k == 1 and ((x.shape[2] * x.shape[3]) % 4 == 0 or PAD_GRAD_WEIGHT_3X3):
-        B, HW = x.shape[0], x.shape[2] * x.shape[3]
-        nbytes = _size('kgdet_conv1x1_grad_weight_workspace_bytes', B, O, C, HW)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-        gw = torch.empty_like(weight)
-        sums = torch.empty((2, O), dtype=torch.float32, device=x.device)
-        _lib.check(L.kgdet_conv1x1_grad_weight_fold(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, HW, ws.data_ptr(), nbytes,
-                                                    weight.data_ptr(), s.data_ptr(), mean.data_ptr(), var.data_ptr(), eps,
-                                                    bn_partial.data_ptr(), P, sums[0].data_ptr(),
-                                                    sums[1].data_ptr() if want_gamma else None, _stream()), 'conv1x1_grad_weight_fold')
-        return gw, sums
-    return None
+    grad_gamma) from ONE launch behind the split kernel -- or None where grad_weight takes MIOpen (grad_weight_fold_route).
+    ``bn_partial=None``: the per-channel sums of gy are formed inside the weight-gradient kernel."""
+    route = grad_weight_fold_route(x, weight)
+    if not route:
+        return None
+    sums = torch.empty((2, weight.shape[0]), dtype=torch.float32, device=x.device)
+    gw = _grad_weight_launch('kgdet_conv%dx%d_grad_weight' % (route, route), x, weight, gy, (
+        weight.data_ptr(), s.data_ptr(), mean.data_ptr(), var.data_ptr(), eps,
+        bn_partial.data_ptr() if bn_partial is not None else None, P if bn_partial is not None else 0,
+        sums[0].data_ptr(), sums[1].data_ptr() if want_gamma else None))
+    return gw, sums
 
 
 def grad_input(weight, img_t, gy, residual=None, gate=None):
@@ -436,45 +405,9 @@ def conv_split(x, weight):
     return _ConvSplit.apply(x, weight)
 
 
-PAD_ODD_MAPS = _os.environ.get('KGDET_PAD_ODD_MAPS', '1') == '1'     # 0: maps with an odd pixel count stay on MIOpen (A/B)
-
-
-def odd_map_applicable(x, weight, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1):
-    """a map with an odd number of pixels (13 x 21, 7 x 11: the two coarsest levels of a five-level head) that the split kernels
-    take once ONE zero column is appended: for a 1x1 / 3x3 stride-1 convolution with its own zero padding the appended column
-    reads as that padding, so the first W output columns are the convolution of the unpadded map.  (MIOpen's fp32 Winograd
-    kernel costs ~47 us per pass whatever the map size: 47 launches, 1.8 ms of a config-5 step.)"""
-    return (PAD_ODD_MAPS and x.dim() == 4 and (x.shape[2] * x.shape[3]) % 2 == 1 and x.shape[2] % 2 == 1 and x.is_cuda
-            and x.dtype == torch.float32 and x.is_contiguous()
-            and applicable(_PadProbe(x), weight, stride, padding, dilation, groups))
-
-
-class _PadProbe(object):
-    """what `applicable` asks of a tensor, for x with one more column (no allocation)"""
-
-    def __init__(self, x):
-        self.is_cuda, self.dtype = x.is_cuda, x.dtype
-        self.shape = (x.shape[0], x.shape[1], x.shape[2], x.shape[3] + 1)
-
-    def dim(self):
-        return 4
-
-    def is_contiguous(self):
-        return True
-
-
-def pad_odd(x):
-    return torch.nn.functional.pad(x, (0, 1))
-
-
-def unpad_odd(y, width):
-    return y[..., :width].contiguous()
-
-
 conv1x1 = conv_split
 
 
-BIAS_GRAD_IN_WGRAD = _os.environ.get('KGDET_BIAS_GRAD_IN_WGRAD', '1') == '1'     # 0: gy.sum((0, 2, 3)) as its own reduce launch (A/B)
 _ones_cache = {}
 
 
@@ -505,23 +438,16 @@ class _ConvBiasAct(torch.autograd.Function):
             gy = torch.ops.aten.threshold_backward(gy, y, 0)
         gy = gy.contiguous()
         gx = grad_input(weight, ctx.img_t, gy) if ctx.needs_input_grad[0] else None
-        if BIAS_GRAD_IN_WGRAD and ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and grad_weight_fold_route(x, weight):
+        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and grad_weight_fold_route(x, weight):
             # the bias gradient = the row sums of grad_y, which the weight-gradient kernel forms on its way (the folded-BatchNorm
             # variant with s = 1: grad_w = 1 * G, grad_beta = the row sums) -- instead of one more pass over grad_y per convolution
             # (45 reduce launches of a config-5 step, 11 of a KGDet step)
             one = _ones(weight.shape[0], weight.device)
-            res = grad_weight_fold(x, weight, gy, one, one, one, 0.0, None, 0, want_gamma=False)
-            if res is not None:
-                return gx, res[0], res[1][0], None
+            gw, sums = grad_weight_fold(x, weight, gy, one, one, one, 0.0, None, 0, want_gamma=False)
+            return gx, gw, sums[0], None
         gw = grad_weight(x, weight, gy) if ctx.needs_input_grad[1] else None
         gb = gy.sum((0, 2, 3)) if ctx.needs_input_grad[2] else None
         return gx, gw, gb, None
-
-
-CACHE_INFER_CASTS = _os.environ.get('KGDET_CACHE_INFER_CASTS', '1') == '1'     # 0: autocast casts weights and biases per batch (A/B)
-
-
-GEMM_1X1_NCHW = _os.environ.get('KGDET_INFER_GEMM_1X1_NCHW', '1') == '1'     # 0: MIOpen for the head's 1x1 output convolutions (A/B)
 
 
 # module -> (key, reduced-precision weight, bias).  Weak keys, module-level: the copies are neither deep-copied nor pickled with
@@ -536,10 +462,10 @@ def invalidate_inference_caches():
     weight-averaging utilities, some checkpoint loaders) changes none of the three -- callers that do that must call this.
     ``checkpoint.load_checkpoint`` and the detector's ``train()`` / ``eval()`` (detector.py: every switch of mode, so that weights
     stepped by a replayed HIP graph -- ``runner.GraphedTrainStep`` -- are never evaluated through stale copies) do; ``ResNet.train()``
-    alone clears the folded-backbone cache only."""
-    global _fold_flat
+    alone clears the folded-backbone cache only.  The training step's folded-BatchNorm state (`_fold_entries`, `_fold_flat`) is
+    NOT among them: it is keyed on the BatchNorm tensors' identities and pointers, its values are recomputed from those tensors
+    at every scope entry -- a ``.data`` write cannot leave it stale -- and a captured step keeps writing its buffers."""
     _cast_cache.clear()
-    _fold_flat = None
     from . import backbone, dcn
     backbone.clear_fold_cache()
     dcn.clear_pack_cache()
@@ -549,7 +475,7 @@ def conv_infer(conv, x):
     """``conv(x)``; inference under autocast keeps the reduced-precision copies of weight and bias across batches (autocast's own
     cache ends with its context: a batch re-cast the head's nine 3x3 weights, the 1x1 output weights and every bias -- ~30 launches,
     ~120 us of a 7 ms batch).  The copies follow the parameters' version counters."""
-    if (CACHE_INFER_CASTS and type(conv) is torch.nn.Conv2d and not torch.is_grad_enabled() and x.is_cuda
+    if (type(conv) is torch.nn.Conv2d and not torch.is_grad_enabled() and x.is_cuda
             and torch.is_autocast_enabled() and conv.weight.dtype == torch.float32 and conv.padding_mode == 'zeros'):
         dt = torch.get_autocast_dtype('cuda')
         # channels-last activations meet a channels-last weight: MIOpen then runs its NHWC kernel as it is, without the
@@ -564,7 +490,7 @@ def conv_infer(conv, x):
                 w = w.contiguous(memory_format=torch.channels_last)
             c = (key, w, None if conv.bias is None else conv.bias.detach().to(dt))
             _cast_cache[conv] = c
-        if (GEMM_1X1_NCHW and not cl and x.dim() == 4 and x.is_contiguous() and x.dtype == dt and conv.kernel_size == (1, 1)
+        if (not cl and x.dim() == 4 and x.is_contiguous() and x.dtype == dt and conv.kernel_size == (1, 1)
                 and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1):
             # a 1x1 convolution of an NCHW tensor (the deformable stages' outputs) IS W [Cout, Cin] @ x[b] [Cin, H*W]: one
             # batched GEMM in place, where MIOpen converts the activation to NHWC, convolves and converts back (+ a bias pass)
@@ -584,9 +510,6 @@ def conv_bias_act(conv, x, relu=False):
             and conv.bias.dtype == torch.float32
             and applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
         return _ConvBiasAct.apply(x, conv.weight, conv.bias, relu)
-    if (type(conv) is torch.nn.Conv2d and conv.bias is not None and torch.is_grad_enabled() and conv.bias.dtype == torch.float32
-            and odd_map_applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
-        return unpad_odd(_ConvBiasAct.apply(pad_odd(x), conv.weight, conv.bias, relu), x.shape[3])
     y = conv_infer(conv, x)
     return torch.relu(y) if relu else y
 
@@ -594,7 +517,7 @@ def conv_bias_act(conv, x, relu=False):
 class _ConvSplitStride2(torch.autograd.Function):
     """3x3 stride-2 padding-1 convolution: forward on conv_nn<9> (MIOpen's fp32 strided kernels run at 15-20 TFLOP/s),
     grad_input on conv3x3_s2_grad_input (four parity classes), grad_weight on a gather of the nine strided views + the 1x1
-    weight-gradient GEMM (round 6); MIOpen behind the switches."""
+    weight-gradient GEMM (round 6); MIOpen for the channel counts those two do not take."""
 
     @staticmethod
     def forward(ctx, x, weight):
@@ -608,28 +531,21 @@ class _ConvSplitStride2(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         gy = gy.contiguous()
         gx = None
-        if ctx.needs_input_grad[0] and STRIDE2_GRAD_INPUT and weight.shape[0] % 16 == 0:
+        if ctx.needs_input_grad[0] and weight.shape[0] % 16 == 0:
             # the four parity classes of the output pixels on the patch kernel (csrc/dense_forward.hip conv3x3_s2_grad_input)
             img_t = ctx.img_t if ctx.img_t is not None else _pack(weight, True)
             gx = torch.empty_like(x)
-            _lib.check(_lib_sizes().kgdet_conv3x3_s2_grad_input(
+            _lib.check(_library().kgdet_conv3x3_s2_grad_input(
                 img_t.data_ptr(), gy.data_ptr(), gx.data_ptr(), x.shape[0], x.shape[1], weight.shape[0], x.shape[2], x.shape[3],
                 _stream()), 'conv3x3_s2_grad_input')
         need_gx = ctx.needs_input_grad[0] and gx is None
         gw = None
         need_gw = ctx.needs_input_grad[1]
-        if need_gw and STRIDE2_GRAD_WEIGHT and (weight.shape[0] * weight.shape[1]) % 2 == 0:
+        if need_gw and (weight.shape[0] * weight.shape[1]) % 2 == 0:
             # the nine strided views of x gathered once, then the 1x1 weight-gradient GEMM over (tap, channel) columns
             # (csrc/dense_grad_weight.hip kgdet_conv3x3_s2_grad_weight): MIOpen's igemm_wrw + its layout transposes were the last vendor
             # kernels of the training step
-            L = _lib_sizes()
-            B, C, H, W = x.shape
-            O = weight.shape[0]
-            nbytes = _size('kgdet_conv3x3_s2_grad_weight_workspace_bytes', B, O, C, H, W)
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-            gw = torch.empty_like(weight)
-            _lib.check(L.kgdet_conv3x3_s2_grad_weight(gy.data_ptr(), x.data_ptr(), gw.data_ptr(), B, O, C, H, W, ws.data_ptr(), nbytes,
-                                                      _stream()), 'conv3x3_s2_grad_weight')
+            gw = _grad_weight_launch('kgdet_conv3x3_s2_grad_weight', x, weight, gy)
             need_gw = False
         if need_gx or need_gw:
             gx2, gw2, _ = torch.ops.aten.convolution_backward(
@@ -639,19 +555,13 @@ class _ConvSplitStride2(torch.autograd.Function):
         return gx, gw
 
 
-STRIDE2 = _os.environ.get('KGDET_CONV_S2', '1') == '1'
-STRIDE2_GRAD_INPUT = _os.environ.get('KGDET_CONV_S2_GI', '1') == '1'    # 0: MIOpen for the stride-2 grad_input (A/B)
-STRIDE2_GRAD_WEIGHT = _os.environ.get('KGDET_CONV_S2_GW', '1') == '1'   # 0: MIOpen for the stride-2 grad_weight (A/B)
-
-
 def applicable_stride2(x, weight, stride, padding, dilation, groups):
-    return (ENABLED and STRIDE2 and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4
+    return (ENABLED and x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4
             and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) == (2, 2) and tuple(padding) == (1, 1)
             and tuple(dilation) == (1, 1) and groups == 1 and x.is_contiguous() and weight.shape[1] % 16 == 0
             # (an odd number of OUTPUT pixels -- 25 x 42 -> 13 x 21 -> 7 x 11, config 5's two extra FPN levels -- in place like the
             #  stride-1 kernels since round 6: MIOpen's split-K forward for them adds with float atomics, and everything computed on
             #  those two levels differed in the last bits from run to run)
-            and (((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) % 2 == 0 or DIRECT_ODD_MAPS)
             and ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2) >= 4 and not torch.is_autocast_enabled())
 
 

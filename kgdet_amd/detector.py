@@ -183,7 +183,7 @@ class RepPointsDetectorKp(nn.Module):
         # operands, folded conv+BN weights).  Those caches are cleared on mode switches / when they fill up, which
         # would free memory the graph still reads: the graph keeps its own strong references.
         from . import backbone, dcn
-        run.pinned = ([v[2] for v in dcn._pack_cache.values()], [v[1:4] for v in backbone._fold_cache.values()])
+        run.pinned = ([v[2] for v in dcn._pack_cache.values()], [(v.weight, v.bias, v.packed) for v in backbone._fold_cache.values()])
         return run
 
     def simple_test(self, img, img_meta, rescale=False):

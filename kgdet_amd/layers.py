@@ -246,9 +246,6 @@ class ConvModule(nn.Module):
                 if (type(conv) is nn.Conv2d and conv.bias is None and torch.is_grad_enabled()
                         and conv1x1.applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
                     x = conv1x1.conv_split(x, conv.weight)     # fp32 training: split-operand MFMA kernels (csrc/dense_forward.hip)
-                elif (type(conv) is nn.Conv2d and conv.bias is None and torch.is_grad_enabled()
-                        and conv1x1.odd_map_applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
-                    x = conv1x1.unpad_odd(conv1x1.conv_split(conv1x1.pad_odd(x), conv.weight), x.shape[3])
                 elif (type(conv) is nn.Conv2d and torch.is_grad_enabled()
                         and conv1x1.applicable_stride2(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups)):
                     # (the FPN's extra levels: 3x3 stride 2.  MIOpen's fp32 forward for the 13 x 21 and 7 x 11 outputs splits K with

@@ -511,11 +511,12 @@ def test_conv1x1_not_applicable_cases_fall_back():
     w3 = torch.randn(32, 64, 3, 3, device='cuda')
     assert c1.applicable(x, w3, padding=(1, 1)) and not c1.applicable(x, w3) and not c1.applicable(x, w3, padding=(1, 1), dilation=(2, 2))
     assert not c1.applicable(x, w3, stride=(2, 2), padding=(1, 1)) and not c1.applicable(x, torch.randn(32, 64, 5, 5, device='cuda'), padding=(2, 2))
-    assert c1.applicable(torch.randn(2, 40, 8, 8, device='cuda'), torch.randn(32, 40, 1, 1, device='cuda')) == c1.RAGGED_1X1
+    assert c1.applicable(torch.randn(2, 40, 8, 8, device='cuda'), torch.randn(32, 40, 1, 1, device='cuda'))     # ragged 1x1: any channel counts
     assert not c1.applicable(torch.randn(2, 40, 8, 8, device='cuda'), torch.randn(32, 40, 3, 3, device='cuda'), padding=(1, 1))
     assert not c1.applicable(torch.randn(2, 7, 8, 8, device='cuda'), torch.randn(5, 7, 1, 1, device='cuda'))     # (the weight-gradient sum handles pairs)
-    assert c1.applicable(torch.randn(2, 64, 3, 3, device='cuda'), w) == c1.DIRECT_ODD_MAPS     # odd H*W: in place since round 4
+    assert c1.applicable(torch.randn(2, 64, 3, 3, device='cuda'), w)                           # odd H*W: in place since round 4
     assert not c1.applicable(torch.randn(2, 64, 1, 3, device='cuda'), w)                       # fewer than 4 pixels
+    assert not c1.applicable(torch.randn(2, 64, 3, 1, device='cuda'), w)
     with torch.autocast('cuda', dtype=torch.bfloat16):
         assert not c1.applicable(x, w)
 
@@ -789,6 +790,44 @@ def test_weight_gradient_kernels_sum_the_rows_of_grad_y(B, C, O, H, W, k):
         assert (got[0].double() - beta).abs().max().item() <= 1e-5 * beta.abs().max().item()
         assert (got[1].double() - gamma).abs().max().item() <= 2e-4 * gamma.abs().max().item()
     assert (gw_b.double() - G * s.double().view(-1, 1, 1, 1)).abs().max().item() <= 2e-4 * G.abs().max().item() * 1.5
+
+
+@pytest.mark.gpu
+def test_folded_batchnorm_flat_buffers_survive_invalidate_inference_caches():
+    """conv1x1._fold_flat owns the S / T / TMP / EPS buffers that a (captured) training step writes through raw pointers: it is
+    training state, and conv1x1.invalidate_inference_caches() -- the detector calls it on every train() / eval() switch -- must
+    neither drop nor move them; the folded step after the call equals the one before it bit for bit."""
+    from kgdet_amd import backbone as bb, conv1x1
+    torch.manual_seed(4)
+    conv = torch.nn.Conv2d(16, 16, 1, bias=False).cuda()
+    bn = torch.nn.BatchNorm2d(16).cuda().eval()
+    bn.running_mean.normal_(0, 0.1); bn.running_var.uniform_(0.5, 1.5)
+    bn.weight.data.uniform_(0.5, 1.5); bn.bias.data.normal_(0, 0.1)
+    x = torch.randn(1, 16, 2, 2, device='cuda', requires_grad=True)
+    gy = torch.randn(1, 16, 2, 2, device='cuda')
+    params = (x, conv.weight, bn.weight, bn.bias)
+
+    def step():
+        with conv1x1.step_scope():
+            y = bb.conv_bn(conv, bn, x, relu=True)
+        return (y.detach().clone(), type(y.grad_fn).__name__) + torch.autograd.grad(y, params, gy)
+
+    conv1x1._entries.clear(); conv1x1._fold_entries.clear()
+    try:
+        assert step()[1] == '_ConvBNActBackward'          # the pair joins the set
+        second = step()                                   # the first folded scope
+        assert second[1] == '_ConvBNActFoldBackward' and len(conv1x1._fold_entries) == 1
+        flat = conv1x1._fold_flat
+        ptrs = [t.data_ptr() for t in (flat.S, flat.T, flat.TMP, flat.EPS)]
+        conv1x1.invalidate_inference_caches()
+        assert conv1x1._fold_flat is flat
+        third = step()
+        assert conv1x1._fold_flat is flat and [t.data_ptr() for t in (flat.S, flat.T, flat.TMP, flat.EPS)] == ptrs
+        assert third[1] == second[1] and len(third) == 6
+        for a, b in zip(second[:1] + second[2:], third[:1] + third[2:]):
+            assert torch.equal(a, b)
+    finally:
+        conv1x1._entries.clear(); conv1x1._fold_entries.clear()
 
 
 @pytest.mark.gpu

@@ -13,7 +13,7 @@ for B, C, O, H, W in shapes:
         y = c1._ConvSplit.apply(x, w); y.backward(gy)
     for _ in range(3): run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    L = c1._lib_sizes()
+    L = c1._library()
     nbytes = L.kgdet_conv1x1_grad_weight_workspace_bytes(ctypes.c_int64(B), ctypes.c_int32(O), ctypes.c_int32(C), ctypes.c_int64(H * W))
     ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda'); gw = torch.empty_like(w)
     from kgdet_amd import _lib
