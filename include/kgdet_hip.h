@@ -47,7 +47,13 @@ int kgdet_conv_pack(const float *w, int32_t O, int32_t C, int32_t taps, int32_t 
  * (1e-4 of the output scale at 1e-3) -- the outputs of BatchNorm / GroupNorm-normalised layers sit inside the envelope;
  * format 0 has no floor and 16 bits.  An image packed with format f must be applied with format f; only
  * forward images (transpose = 0) take format 1.  kgdet_conv_pack_multi: bit 62 of a descriptor's last word selects
- * format 1 for that row's forward image.  The plain entry points are format 0. */
+ * format 1 for that row's forward image.  The plain entry points are format 0.
+ * The library does not enforce the envelope: outside it format 1 clamps and still returns KGDET_OK.  The check is the caller's --
+ * kgdet_range_scan_multi below scans the weights (limit |w s| <= 65504 / 2^8 = 255.875, s the folded BatchNorm scale), and
+ * kgdet_amd/numerics.py runs it when a checkpoint is loaded and at the end of every epoch, policy KGDET_ENVELOPE = bf16 (default:
+ * a violating layer's forward image is packed and applied in format 0, which has no range limit) | raise | warn | off.  Not
+ * covered: activations of normal runs (numerics.audit scans them on request against 65504 / 131008), the deformable convolutions'
+ * operands (packed on their own path) and gradients (format 0 already). */
 int kgdet_conv_pack_fmt(const float *w, int32_t O, int32_t C, int32_t taps, int32_t transpose, void *packed,
                         int32_t operand_format, void *stream);
 int kgdet_conv_pack_both_fmt(const float *w, int32_t O, int32_t C, int32_t taps, void *packed, void *packed_t,
@@ -527,6 +533,28 @@ int kgdet_multi_clip_sgd(const int64_t *table_dev, int32_t n, int64_t total_bloc
 int kgdet_multi_clip_sgd_dev(const int64_t *table_dev, int32_t n, int64_t total_blocks, const float *norm /*nullable*/,
                              float max_norm, float *sched, const float *lr_ring /*nullable*/, int32_t ring, double momentum,
                              double dampening, float weight_decay, int32_t nesterov, void *stream);
+
+/*
+ * Range scan of n_rows fp32 tensors in ONE kernel launch (csrc/range_scan.hip) -- the check of the format-1 (fp16 parts) envelope
+ * of the dense convolutions above that kgdet_amd/numerics.py runs when a checkpoint is loaded and at the end of an epoch.  No
+ * reference counterpart.  table_dev: device table of n_rows x 8 int64
+ *   {tensor (float, 4-byte aligned), count, inner, gamma or 0, var or 0, bits of eps, bits of hi1 | bits of hi2 << 32, first block}
+ * first block = running sum of kgdet_range_scan_blocks(count) over the preceding rows, total_blocks = the sum over all rows (a row
+ * has at most 256 blocks, which stride over its chunks of kgdet_range_scan_chunk() elements).  inner > 0 and var != 0: element i is
+ * multiplied by s[i / inner], s[o] = gamma[o] / sqrtf(var[o] + eps) (gamma 0: 1 / sqrtf(var[o] + eps)) -- the scale of a
+ * frozen-statistics BatchNorm folded into an [O, C, k, k] weight with inner = C k k; gamma and var hold ceil(count / inner) floats.
+ * Otherwise the values are scanned as they are.  records: device, n_rows x 4 uint32, OVERWRITTEN by every call:
+ *   {bits of max |v s| over the finite products (0 when there is none), number of non-finite products,
+ *    number of products with |v s| > hi1, number with |v s| > hi2 (an infinite product counts in both, a NaN in neither)}
+ * Products are float32, rounded once.  Integer atomics only: the record does not depend on the schedule.  The envelope's limits
+ * as the caller passes them: a (folded) forward weight hi1 = 65504 / 2^8 = 255.875 (the image stores w s 2^8 in fp16 parts: beyond,
+ * the kernels clamp and still return KGDET_OK); an activation hi1 = 65504 (fp32-class up to here), hi2 = 131008 (11 bits up to
+ * here, clamped beyond).  Not covered by the scan's callers: activations of normal runs (numerics.audit scans them on request),
+ * the deformable convolutions' operands (their pack path is separate) and gradients (bf16 parts already: no range limit).
+ */
+int32_t kgdet_range_scan_chunk(void);
+int64_t kgdet_range_scan_blocks(int64_t count);
+int kgdet_range_scan_multi(const int64_t *table_dev, int32_t n_rows, int64_t total_blocks, uint32_t *records, void *stream);
 
 /*
  * GroupNorm (+ ReLU) of the ConvModules of the head towers and the neck as one pass each way -- ATen runs it as ten kernels

@@ -51,7 +51,7 @@ def _stem_conv(conv, x):
         if hit is None or hit[0] != key or hit[2]() is not w:
             w160 = torch.zeros((64, 160), dtype=torch.float32, device=w.device)
             w160[:, :147] = w.detach().reshape(64, 147)
-            hit = (key, conv1x1._pack(w160.view(64, 160, 1, 1), False), weakref.ref(w))
+            hit = (key, conv1x1._pack(w160.view(64, 160, 1, 1), False, f16=conv1x1.forward_f16(w)), weakref.ref(w))
             _stem_cache[id(conv)] = hit
         B, _, H, W = x.shape
         y = torch.empty((B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
@@ -111,6 +111,16 @@ _fold_cache = {}   # (id(conv), bf16?) -> _Folded
 def clear_fold_cache():
     _fold_cache.clear()
     _stem_cache.clear()
+
+
+def drop_folded(weight):
+    """drop the folded copies and the stem pack made from ONE weight (conv1x1.set_bf16_parts: their images have the old format)"""
+    for cache, conv_of in ((_fold_cache, lambda hit: hit.conv()), (_stem_cache, None)):
+        for k in list(cache):
+            hit = cache[k]
+            w = hit[2]() if conv_of is None else getattr(conv_of(hit), 'weight', None)
+            if w is None or w is weight:
+                del cache[k]
 
 
 def _epilogue_(y, bias, residual, relu):
@@ -558,7 +568,8 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
             w = w.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         packed = None
         if not bf16 and conv1x1.applicable(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
-            packed = conv1x1._pack(w.contiguous(), False)     # fp32 inference: split-bf16 MFMA kernels, packed once
+            # fp32 inference: split MFMA kernels, packed once -- in the format of the convolution's own weight (conv1x1.set_bf16_parts)
+            packed = conv1x1._pack(w.contiguous(), False, f16=conv1x1.forward_f16(conv.weight))
         hit = _Folded(weakref.ref(conv), w, shift.detach().float().contiguous(), packed, ver,
                       shift.detach().to(torch.bfloat16).contiguous() if bf16 else None)
         _fold_cache[(id(conv), bf16)] = hit

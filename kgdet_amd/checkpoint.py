@@ -52,6 +52,11 @@ def load_checkpoint(model, filename, map_location=None, strict=False):
     # derived weight images (folded conv+BN weights, packed deformable-conv operands) belong to the old weights
     from . import conv1x1
     conv1x1.invalidate_inference_caches()
+    # the loaded weights against the envelope of the fp16-part convolutions (numerics.py, policy KGDET_ENVELOPE); CUDA models only:
+    # a CPU model never reaches the kernels, and the library is not loaded for it
+    if os.environ.get('KGDET_ENVELOPE', 'bf16') != 'off' and any(p.is_cuda for p in target.parameters()):
+        from . import numerics
+        numerics.enforce(target)
     return checkpoint
 
 

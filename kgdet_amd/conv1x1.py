@@ -63,6 +63,10 @@ _PROTOTYPES = (
     ('kgdet_conv3x3_s2_grad_weight', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     ('kgdet_conv1x1_grad_weight_fold', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _sz] + _FOLD_TAIL + [_vp]),
     ('kgdet_conv3x3_grad_weight_fold', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz] + _FOLD_TAIL + [_vp]),
+    # numerics.py
+    ('kgdet_range_scan_chunk', _i32, []),
+    ('kgdet_range_scan_blocks', _i64, [_i64]),
+    ('kgdet_range_scan_multi', _int, [_vp, _i32, _i64, _vp, _vp]),
     # backbone.py
     ('kgdet_stem_conv7x7_s2_fmt', _int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     ('kgdet_bias_act', _int, [_vp, _vp, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp]),
@@ -110,27 +114,93 @@ def _mark(img, f16):
     return img
 
 
-def _pack(weight, transpose):
-    """weight [O, C, k, k] -> operand image (forward: rows O; transpose: rows C with mirrored taps)"""
+# ---- one layer on bf16 parts (kgdet_amd/numerics.py: a weight that leaves the fp16 parts' envelope, |w s| 2^8 <= 65504) ------
+class EnvelopeError(RuntimeError):
+    """an operand outside the envelope of the fp16-part convolutions under the policy 'raise', a non-finite weight, or a change
+    of a layer's format underneath a captured training step (also numerics.EnvelopeError)"""
+
+
+_bf16_parts = {}     # id(weight) -> weakref to the parameter whose FORWARD images take bf16 parts whatever FORWARD_F16 says
+_captures = {}       # id(step) -> weakref to a runner.GraphedTrainStep whose graph holds launches with the formats baked in
+
+
+def bf16_parts(weight):
+    r = _bf16_parts.get(id(weight))
+    return r is not None and r() is weight
+
+
+def forward_f16(weight, f16=None):
+    """the format of ``weight``'s forward image: ``f16`` when given, else FORWARD_F16 unless `set_bf16_parts` routed the weight"""
+    if f16 is not None:
+        return bool(f16)
+    return FORWARD_F16 and not (_bf16_parts and bf16_parts(weight))
+
+
+def register_capture(step):
+    key = id(step)
+    _captures[key] = weakref.ref(step, lambda _r, key=key: _captures.pop(key, None))
+
+
+def release_capture(step):
+    _captures.pop(id(step), None)
+
+
+def set_bf16_parts(weight, on=True):
+    """Route the forward operand images of ONE weight (a convolution's parameter; with a folded BatchNorm the images of w * s) to
+    bf16 parts -- no range limit, ~5e-6 of the output scale instead of fp32-class -- or back (``on=False``).  The persistent
+    images of the weight are re-marked and packed again before their next use, the pack table and the inference-time folded
+    copies of the weight are dropped.  Returns True when the route changed.  A captured training step (runner.GraphedTrainStep)
+    of a model that holds the weight has the old format -- and the old table's address -- in its launches: EnvelopeError then;
+    build the step again (`GraphedTrainStep.retire()` first; `Runner.check_envelope` does both)."""
+    global _table
+    if bf16_parts(weight) == bool(on):
+        return False
+    for r in list(_captures.values()):
+        step = r()
+        if step is not None and any(p is weight for p in step.model.parameters()):
+            raise EnvelopeError('the operand format of a convolution weight %s cannot change underneath a captured training '
+                                'step: retire() the GraphedTrainStep, change the route and build the graphed step again'
+                                % (tuple(weight.shape),))
+    key = id(weight)
+    if on:
+        _bf16_parts[key] = weakref.ref(weight, lambda _r, key=key: _bf16_parts.pop(key, None))
+    else:
+        del _bf16_parts[key]
+    f16 = forward_f16(weight)
+    for entries in (_entries, _fold_entries):
+        e = entries.get(key)
+        if e is not None and e.ref() is weight:
+            _mark(e.img, f16)
+            e.token = 0          # (packed again, in the new format, before it is next used: forward_images / the next scope's launch)
+    _table = None
+    from . import backbone
+    backbone.drop_folded(weight)
+    return True
+
+
+def _pack(weight, transpose, f16=None):
+    """weight [O, C, k, k] -> operand image (forward: rows O; transpose: rows C with mirrored taps); ``f16``: the forward
+    image's format when the caller knows it (an image of a tensor DERIVED from a routed parameter), default `forward_f16`"""
     L = _library()
     O, C, taps = weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3]
     M, K = (C, O) if transpose else (O, C)
     img = torch.empty(_size('kgdet_conv_packed_bytes', M, K, taps), dtype=torch.uint8, device=weight.device)
-    f16 = FORWARD_F16 and not transpose
+    f16 = forward_f16(weight, f16) and not transpose
     _lib.check(L.kgdet_conv_pack_fmt(weight.data_ptr(), O, C, taps, 1 if transpose else 0, img.data_ptr(), 1 if f16 else 0,
                                      _stream()), 'conv_pack')
     return _mark(img, f16)
 
 
-def _pack_both(weight):
+def _pack_both(weight, f16=None):
     """forward and grad_input images of one weight in one launch"""
+    f16 = forward_f16(weight, f16)
     L = _library()
     O, C, taps = weight.shape[0], weight.shape[1], weight.shape[2] * weight.shape[3]
     img = torch.empty(_size('kgdet_conv_packed_bytes', O, C, taps), dtype=torch.uint8, device=weight.device)
     img_t = torch.empty(_size('kgdet_conv_packed_bytes', C, O, taps), dtype=torch.uint8, device=weight.device)
     _lib.check(L.kgdet_conv_pack_both_fmt(weight.data_ptr(), O, C, taps, img.data_ptr(), img_t.data_ptr(),
-                                          1 if FORWARD_F16 else 0, _stream()), 'conv_pack_both')
-    return _mark(img, FORWARD_F16), _mark(img_t, False)
+                                          1 if f16 else 0, _stream()), 'conv_pack_both')
+    return _mark(img, f16), _mark(img_t, False)
 
 
 def _apply(img, x, M, taps, stride=1, bias=None, residual=None, relu=False, gate=None):
@@ -269,7 +339,7 @@ def fold_images(weight, bn):
         e = _FoldEntry()
         e.ref, e.bn, e.ptr, e.token = weakref.ref(weight), weakref.ref(bn), weight.data_ptr(), 0
         e.img = _mark(torch.empty(_size('kgdet_conv_packed_bytes', O, C, taps), dtype=torch.uint8, device=weight.device),
-                      FORWARD_F16)
+                      forward_f16(weight))
         e.img_t = _mark(torch.empty(_size('kgdet_conv_packed_bytes', C, O, taps), dtype=torch.uint8, device=weight.device), False)
         e.s = e.t = None
         _fold_entries[id(weight)] = e

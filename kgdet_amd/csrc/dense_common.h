@@ -71,6 +71,8 @@ constexpr float kF16WeightScale = 256.0f;
 // of a channel with a tiny running variance reaches that through w * s * 2^8).  With it: hi = 65504, lo = f16(v - 65504):
 // an 11-bit representation up to 131008 (measured on the GPU: 2e-4 of the output scale) and clamped beyond -- finite; the
 // fp32-class envelope still ends at 65504 (tests/test_gpu_backbone.py::test_fp16_forward_parts_saturate_instead_of_nan).
+// Nothing here enforces the envelope; kgdet_amd/numerics.py checks the weights against it with range_scan.hip (checkpoint load,
+// end of epoch) and routes a layer that leaves it to bf16 parts (policy KGDET_ENVELOPE; include/kgdet_hip.h).
 __device__ __forceinline__ void f16_saturate_on() {
   __builtin_amdgcn_s_setreg(1 /*HW_REG_MODE*/ | (23 << 6) /*offset*/ | (0 << 11) /*size - 1*/, 1u);
 }

@@ -283,6 +283,7 @@ class GraphedTrainStep(object):
         from .optim import FusedClipAdam, FusedClipSGD
         self.model, self.optimizer, self.hook = model, optimizer, opt_hook
         self.static = batch
+        self._rebuild = dict(warmup=warmup, batch_processor=batch_processor)
         self.static_tensors = [batch['img']] + [t for k in ('gt_bboxes', 'gt_labels', 'gt_keypoints') for t in batch.get(k, [])]
         assert all(t.is_cuda for t in self.static_tensors) and model.training
 
@@ -347,6 +348,27 @@ class GraphedTrainStep(object):
                 group['lr'] = lr_host                      # (schedulers keep seeing and setting a float)
         # (the capture itself does not run the step: nothing was counted yet)
         self.steps = 0
+        # the captured launches hold each convolution's operand format and the pack table's address: conv1x1.set_bf16_parts refuses
+        # to change a route of this model until `retire()`
+        from . import conv1x1
+        conv1x1.register_capture(self)
+
+    def retire(self):
+        """give the graph up (its launches bake in the operand formats and table addresses of the capture): after this the routes
+        of the model's convolutions may change (conv1x1.set_bf16_parts); ``recapture()`` builds the step again"""
+        from . import conv1x1
+        torch.cuda.synchronize()
+        conv1x1.release_capture(self)
+        self.graph = self.out = None
+
+    def recapture(self):
+        """a new GraphedTrainStep of the same model, optimizer, hook and input buffers (like the first capture it takes warm-up
+        steps on the batch in the buffers); the steps counted so far carry over"""
+        if self.graph is not None:
+            self.retire()
+        new = GraphedTrainStep(self.model, self.optimizer, self.hook, self.static, **self._rebuild)
+        new.steps = self.steps
+        return new
 
     def load(self, batch):
         new = [batch['img']] + [t for k in ('gt_bboxes', 'gt_labels', 'gt_keypoints') for t in batch.get(k, [])]
@@ -407,6 +429,35 @@ class Runner(object):
         self.log_interval, self.logger, self.batch_processor = log_interval, logger, batch_processor
         self.epoch, self.iter = 0, 0
         self.log_history = []
+        self.graphed = None      # a GraphedTrainStep driven by the caller (`attach_graphed`): re-captured when a layer is rerouted
+
+    def attach_graphed(self, step):
+        """tell the runner about the GraphedTrainStep the caller replays between its epochs: `check_envelope` builds it again when
+        it has to change a convolution's operand format (read ``runner.graphed`` afterwards)"""
+        self.graphed = step
+        return step
+
+    def check_envelope(self):
+        """The envelope of the fp16-part convolutions (numerics.py) on the model's current weights, policy ``KGDET_ENVELOPE``: run
+        at the end of every epoch, before validation and the checkpoint write -- one scan launch and one read-back, nothing inside
+        the step.  CUDA models only.  A reroute underneath a graphed step retires the step first and captures it again.
+        -> the violations that led to a reroute"""
+        target = self.model.module if hasattr(self.model, 'module') else self.model
+        if os.environ.get('KGDET_ENVELOPE', 'bf16') == 'off' or not any(p.is_cuda for p in target.parameters()):
+            return []
+        from . import numerics
+        retired = []
+
+        def before_reroute():
+            if self.graphed is not None and self.graphed.graph is not None:
+                self.graphed.retire()
+                retired.append(self.graphed)
+
+        _, rerouted = numerics.enforce(target, before_reroute=before_reroute)
+        if retired:
+            self.graphed = retired[0].recapture()
+            self.logger('envelope: %d layer(s) rerouted to bf16 parts, the graphed step was captured again' % len(rerouted))
+        return rerouted
 
     def current_lr(self):
         return [g['lr'] for g in self.optimizer.param_groups]
@@ -455,6 +506,7 @@ class Runner(object):
             if set_epoch is not None:
                 set_epoch(self.epoch)
             self.train_epoch(data_loader, to_device)
+            self.check_envelope()
             if self.work_dir is not None and self.ckpt_interval > 0 and self.epoch % self.ckpt_interval == 0:
                 self.save_checkpoint()
             if self.eval_config is not None and self.epoch % self.eval_config.get('interval', 1) == 0:
