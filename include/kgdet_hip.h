@@ -459,6 +459,74 @@ int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_
                              const void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Target assignment + the five loss families of the serial / parallel two-stage heads over the whole pyramid, without
+ * materialised targets.  Replaces, for RepPointsHeadKpSerial / RepPointsHeadKpParallel (reppoints_head_kp_serial.py loss /
+ * loss_single): PointAssigner.assign (core/bbox/assigners/point_assigner.py) for the init stage, bbox_overlaps
+ * (core/bbox/geometry.py) + MaxIoUAssigner.assign_wrt_overlaps with gt_max_assign_all (core/bbox/assigners/
+ * max_iou_assigner.py) for the refine stage, point_target_kp (core/anchor/point_target_kp.py), offset_to_pts and the
+ * FocalLoss / SmoothL1Loss reductions.
+ * Maps per level l (NCHW float32, grid H[l] x W[l], points x = column * stride[l], y = row * stride[l]): cls [B, C, H, W];
+ * kpt_init / kpt_refine [B, 2 K, H, W], (y, x) offset pairs decoded as pred * stride + centre; box_init / box_refine
+ * [B, 4, H, W] = the head's points2bbox of the raw reppoints maps, in stride units: the image-space box is
+ * centre + box * stride, one rounding per operation (what the torch chain hands its assigner, bit for bit).
+ * Init assignment: a ground truth lives on level int((log2(w / scale) + log2(h / scale)) / 2) - log2(stride[0]), clamped to
+ * [0, L); its positives are the pos_num nearest valid points of that level under |(p - centre) / max(size, 1e-6)| (ties: the
+ * lowest point index); a point several ground truths claim goes to the nearest, the earliest on a tie.
+ * Refine assignment, over all levels' points of an image: IoU with the +1 convention of every point's init box; per point the
+ * best IoU (lowest gt on equal values): 0 inside [neg_lo, neg_hi), gt + 1 from pos_iou_thr on, else -1; then every ground
+ * truth whose maximum IoU over the valid points reaches min_pos_iou takes EVERY valid point at exactly that IoU, the last
+ * such ground truth winning.  Invalid points: 0, label weight 0, best IoU -2.
+ * losses[k * L + l], k = cls, bbox_init, bbox_refine, kpt_init, kpt_refine: loss_weight[k] * (sum over level l / num_total);
+ * num_total[0] = init, [1] = refine: sum over the images of max(positives, 1) (cls, *_refine use [1]).  Device scalars;
+ * nothing is read by the host; fixed summation orders.  grad_losses [5 * L] in the same order.  The backward call takes the
+ * forward call's workspace and writes every element of the 5 * L gradient maps.
+ * Workspace layout, N = sum of H[l] * W[l], points image-major then level-major, row-major inside a level; every table starts
+ * on a 256-byte boundary, T = B * N * 4 rounded up to a multiple of 256 bytes:
+ *   byte 0      int32 assigned_init[B][N]    (0 / gt + 1)
+ *   byte T      int32 assigned_refine[B][N]  (-1 / 0 / gt + 1)
+ *   byte 2 T    float best_iou[B][N]
+ *   byte 3 T    internal tables and the per-workgroup partial sums.
+ * Shorter than kgdet_serial_loss_workspace_bytes(): KGDET_E_WORKSPACE.
+ * Cost beyond the configs' pos_num = 1: the init stage makes pos_num passes over a ground truth's level, and one workgroup per
+ * image settles the points several ground truths claim by comparing all num_gt * pos_num selections pairwise (4096^2 at both
+ * limits).
+ * Limits: B <= 16, 1..64 ground truths per image, 1..8 levels whose strides are consecutive powers of two, up to 32768
+ * points per level, pos_num 1..64 and not beyond any image's valid point count on any level.
+ * ------------------------------------------------------------------------------------------ */
+#define KGDET_SERIAL_MAX_LEVELS 8
+typedef struct kgdet_serial_targets {
+  int32_t B, L, num_classes, num_keypoints;
+  int32_t H[KGDET_SERIAL_MAX_LEVELS], W[KGDET_SERIAL_MAX_LEVELS];
+  float stride[KGDET_SERIAL_MAX_LEVELS];
+  int32_t num_gt[KGDET_HEAD_MAX_IMAGES];
+  const float *gt_bboxes[KGDET_HEAD_MAX_IMAGES];     /* [num_gt, 4] */
+  const int64_t *gt_labels[KGDET_HEAD_MAX_IMAGES];   /* [num_gt], NULL: every label 1 */
+  const float *gt_keypoints[KGDET_HEAD_MAX_IMAGES];  /* [num_gt, num_keypoints, 3] (x, y, visibility) */
+  /* valid extent of image b on level l (ceil(pad_shape / stride), clamped to the grid); 0 = the whole grid */
+  int32_t valid_h[KGDET_HEAD_MAX_IMAGES][KGDET_SERIAL_MAX_LEVELS], valid_w[KGDET_HEAD_MAX_IMAGES][KGDET_SERIAL_MAX_LEVELS];
+} kgdet_serial_targets;
+typedef struct kgdet_serial_loss_cfg {
+  int32_t pos_num;                 /* init: PointAssigner.pos_num */
+  float scale;                     /* init: PointAssigner.scale */
+  float pos_iou_thr, neg_lo, neg_hi, min_pos_iou;   /* refine: MaxIoUAssigner (a float neg_iou_thr t is the range [0, t)) */
+  float pos_weight;                /* label weight of refine positives (train_cfg.refine.pos_weight <= 0 -> 1) */
+  float point_base_scale;          /* normalize_term of level l = point_base_scale * stride[l] */
+  float gamma, alpha;              /* FocalLoss */
+  float beta[4];                   /* SmoothL1Loss: bbox_init, bbox_refine, kpt_init, kpt_refine */
+  float loss_weight[5];            /* cls, bbox_init, bbox_refine, kpt_init, kpt_refine */
+} kgdet_serial_loss_cfg;
+typedef struct kgdet_serial_maps {
+  float *cls[KGDET_SERIAL_MAX_LEVELS], *box_init[KGDET_SERIAL_MAX_LEVELS], *box_refine[KGDET_SERIAL_MAX_LEVELS],
+      *kpt_init[KGDET_SERIAL_MAX_LEVELS], *kpt_refine[KGDET_SERIAL_MAX_LEVELS];
+} kgdet_serial_maps;
+size_t kgdet_serial_loss_workspace_bytes(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg);
+int kgdet_serial_loss_forward(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, const kgdet_serial_maps *maps,
+                              float *losses, float *num_total, void *workspace, size_t workspace_bytes, void *stream);
+int kgdet_serial_loss_backward(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, const kgdet_serial_maps *maps,
+                               const float *grad_losses, const float *num_total, const kgdet_serial_maps *grads,
+                               const void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Element-wise glue of the KGDet step as single passes (no native function in the reference).
  * kgdet_reppts_offsets_*: the deformable offsets of a Kp3RepBlock from the previous stage's reppoints,
  *   reppoints_head_kp3rep_cas_1_assign_once.py:131-143: for the 2 k^2-channel slices (k = kernel_sizes[0..2], consecutive)

@@ -27,6 +27,7 @@
 #include <float.h>
 
 #include "common.h"
+#include "loss_math.h"
 
 namespace kgdet {
 
@@ -35,39 +36,6 @@ namespace {
 constexpr int kMaxImages = KGDET_HEAD_MAX_IMAGES;
 constexpr int kMaxGt = 64;
 constexpr int kMaxPoints = 4096;
-
-__device__ __forceinline__ double neg_softplus_d(float x) {  // as csrc/focal.hip
-  const int ge = x >= 0;
-  return -1. * x * ge - logf((float)(1. + expf((float)(x - 2. * x * ge))));
-}
-
-// sigmoid_focal_loss_cuda.cu:24-59 (same promotions as csrc/focal.hip)
-__device__ __forceinline__ float focal_fwd(float x, int t, int d, float gamma, float alpha) {
-  const float c1 = (t == (d + 1));
-  const float c2 = ((t >= 0) & (t != (d + 1)));
-  const float zn = (float)(1.0 - alpha), zp = alpha;
-  const float p = (float)(1. / (1. + expf(-x)));
-  const float term1 = powf((float)(1. - p), gamma) * logf(fmaxf(p, FLT_MIN));
-  const float term2 = (float)(powf(p, gamma) * neg_softplus_d(x));
-  float l = 0.0f;
-  l += -c1 * term1 * zp;
-  l += -c2 * term2 * zn;
-  return l;
-}
-
-// :62-97
-__device__ __forceinline__ float focal_bwd(float x, int t, int d, float gamma, float alpha) {
-  const float c1 = (t == (d + 1));
-  const float c2 = ((t >= 0) & (t != (d + 1)));
-  const float zn = (float)(1.0 - alpha), zp = alpha;
-  const float p = (float)(1. / (1. + expf(-x)));
-  const float term1 = (float)(powf((float)(1. - p), gamma) * (1. - p - (p * gamma * logf(fmaxf(p, FLT_MIN)))));
-  const float term2 = (float)(powf(p, gamma) * (neg_softplus_d(x) * (1. - p) * gamma - p));
-  float g = 0.0f;
-  g += -c1 * term1 * zp;
-  g += -c2 * term2 * zn;
-  return g;
-}
 
 // the assignment of point i of image b from the per-gt selections: point_assigner.py:106-117 (`min_dist <
 // assigned_gt_dist[point_index]`, gts in order: the earlier gt keeps a tie)

@@ -21,7 +21,7 @@ import os as _os
 import torch
 import torch.nn as nn
 
-from . import conv1x1, dcn
+from . import conv1x1, dcn, serial_loss
 from .heads import PointHeadMixin
 from .layers import ConvModule, bias_init_with_prob, normal_init, shared_levels
 
@@ -263,6 +263,11 @@ class _RepPointsHeadKpTwoStage(PointHeadMixin, nn.Module):
              gt_bboxes, gt_labels, gt_keypoints, img_metas, cfg, gt_bboxes_ignore=None):
         featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores]
         assert len(featmap_sizes) == len(self.point_generators)
+        # both assignments, the decode and the five losses of every level as five HIP launches (csrc/serial_loss.hip) where the
+        # configuration is the one config 5 trains; anything else takes the torch chain below (KGDET_FUSED_SERIAL_LOSS=0: always)
+        maps = (cls_scores, keypts_preds_init, keypts_preds_refine, reppts_preds_init, reppts_preds_refine)
+        if serial_loss.applicable(self, cfg, *maps, gt_bboxes, gt_labels, gt_keypoints, img_metas, gt_bboxes_ignore):
+            return serial_loss.serial_loss(self, cfg, *maps, gt_bboxes, gt_labels, gt_keypoints, img_metas)
         label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
         device = cls_scores[0].device
 
