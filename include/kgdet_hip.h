@@ -42,7 +42,11 @@ int kgdet_conv_pack(const float *w, int32_t O, int32_t C, int32_t taps, int32_t 
 /* operand_format of the *_fmt entry points: 0 = two bf16 parts per fp32 value (16 mantissa bits; every gradient operand),
  * 1 = two fp16 parts (22 bits, fp32-class results at the same MFMA rate) for FORWARD operands.  Envelope of format 1: weights up
  * to 255 in magnitude (the image stores them scaled by 2^8 so that their lo parts stay normal; the kernels scale the
- * accumulators back), activations of magnitude ~1e-2 .. 6e4 at full accuracy (<= 1e-6 of the output scale); beyond 65504 they
+ * accumulators back) and, for an output channel to keep that accuracy against ITS OWN scale, down to ~5e-4 (2^-11): below, the lo
+ * part of w * 2^8 is an fp16 subnormal with a quantum of 2^-24, i.e. an absolute 2^-33 per weight -- a row of 1e-5 (a BatchNorm
+ * fold scale near zero: a zero-initialised last gamma) keeps 6e-6 of its own output scale, which is still far below 1e-6 of the
+ * tensor's scale next to rows of order 0.1 (tests/test_dense_refs.py measures it on the restated split, the kernels give exactly
+ * that: tests/test_gpu_dense_kernels.py).  Activations of magnitude ~1e-2 .. 6e4 at full accuracy (<= 1e-6 of the output scale); beyond 65504 they
  * saturate, below ~1e-3 the lo part becomes an fp16 subnormal and the error has an ABSOLUTE floor of ~3e-8 per activation
  * (1e-4 of the output scale at 1e-3) -- the outputs of BatchNorm / GroupNorm-normalised layers sit inside the envelope;
  * format 0 has no floor and 16 bits.  An image packed with format f must be applied with format f; only
@@ -84,6 +88,19 @@ size_t kgdet_conv_apply_workspace_bytes(int64_t B, int32_t M, int32_t K, int32_t
                                         int32_t stride); /* mostly 0 */
 int kgdet_conv_apply(const void *packed, const float *x, float *y, int64_t B, int32_t M, int32_t K, int32_t H, int32_t W,
                      int32_t taps, int32_t stride, void *workspace, size_t workspace_bytes, void *stream);
+/* What kgdet_conv_apply* decides for a shape (host code, launches nothing; the launch reads the same plan).  out[]:
+ *   0 patch     1: conv3x3_patch4 (3x3 stride 1), 0: conv_nn
+ *   1 TX, 2 TY  conv3x3_patch4's pixel tile (0 for conv_nn)       3 NB  its 32-pixel blocks per tile: 4 | 5
+ *   4 NW        conv_nn's waves along the pixels: 4 | 5 (128- or 160-pixel tiles)
+ *   5 ks        K parts (> 1: partials in the workspace and a closing pass)
+ *   6 halves    1: conv3x3_patch4<2, 4>, a workgroup per 64-row half
+ *   7 tiles     output tiles (row tiles x pixel tiles x images)       8 n_nt  pixel tiles per image
+ *   9 closer with bias, residual, relu or gate given, 10 closer with none of them:
+ *     0 the kernel's own store, 1 conv1x1_sum_epilogue, 2 conv1x1_sum then kgdet_bias_act (odd pixel count: a gate is refused),
+ *     3 conv1x1_sum */
+#define KGDET_CONV_APPLY_PLAN_WORDS 11
+int kgdet_conv_apply_plan(int64_t B, int32_t M, int32_t K, int32_t H, int32_t W, int32_t taps, int32_t stride,
+                          int32_t out[KGDET_CONV_APPLY_PLAN_WORDS]);
 /* the same with the inference epilogue fused into the store: y = [relu](conv + bias[m] [+ residual]); bias [M] and
  * residual [B, M, Ho, Wo] nullable (the folded-BatchNorm bottleneck at inference, kgdet_amd/backbone.py conv_bn). */
 int kgdet_conv_apply_epilogue(const void *packed, const float *x, float *y, const float *bias, const float *residual,
@@ -113,6 +130,16 @@ int kgdet_conv1x1_grad_weight(const float *grad_y, const float *x, float *grad_w
 size_t kgdet_conv3x3_grad_weight_workspace_bytes(int64_t B, int32_t O, int32_t C, int32_t H, int32_t W);
 int kgdet_conv3x3_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t O, int32_t C,
                               int32_t H, int32_t W, void *workspace, size_t workspace_bytes, void *stream);
+/* What the weight gradients decide for a shape (host code, launches nothing).  taps = 1: H = 1 and W = the pixel count (the
+ * stride-2 route asks with C = 9 * its channels and W = its output pixels).  out[]:
+ *   0 use_ntp   1: conv_ntp, 0: conv_nt8          1 padded   conv_nt8 on pad_rows2's copies
+ *   2 aligned   W % 4 == 0 (conv_ntp<., aligned>) 3 splits   partials the closing pass adds
+ *   4 spi       stages per image                  5 per      stages per split
+ *   6, 7, 8     offsets of the workspace regions (partials, padded copies, per-row sums of grad_y) in units of 256 bytes
+ *   9 tiles     128 x 128 tiles of grad_w */
+#define KGDET_CONV_GRAD_WEIGHT_PLAN_WORDS 10
+int kgdet_conv_grad_weight_plan(int64_t B, int32_t O, int32_t C, int32_t H, int64_t W, int32_t taps,
+                                int32_t out[KGDET_CONV_GRAD_WEIGHT_PLAN_WORDS]);
 
 /* Frozen-statistics BatchNorm (+ residual add) (+ ReLU) in one pass -- the norm_eval=True training path of
  * mmdet/models/backbones/resnet.py:240-262,518-525.  float32, NCHW: x, residual, y [N, C, HW]; gamma, beta (nullable:

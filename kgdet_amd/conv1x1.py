@@ -48,6 +48,8 @@ _FOLD_TAIL = [_vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp]      # w, s, mean, 
 _PROTOTYPES = (
     ('kgdet_conv_packed_bytes', _sz, [_i32, _i32, _i32]),
     ('kgdet_conv_apply_workspace_bytes', _sz, [_i64, _i32, _i32, _i32, _i32, _i32, _i32]),
+    ('kgdet_conv_apply_plan', _int, [_i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    ('kgdet_conv_grad_weight_plan', _int, [_i64, _i32, _i32, _i32, _i64, _i32, _vp]),
     ('kgdet_conv_pack_fmt', _int, [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp]),
     ('kgdet_conv_pack_both_fmt', _int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp]),
     ('kgdet_conv_pack_blocks', _i64, [_i32, _i32, _i32]),

@@ -63,6 +63,9 @@ __device__ __forceinline__ void split8(const float (&v)[8], bf16x8 &hi, bf16x8 &
 // fp16's normal range ends at 6.1e-5: the lo part of a weight of 0.03 (7e-6) would be subnormal and keep ~7 of its 11 bits.
 // The pack kernels therefore store fp16-format weights scaled by kF16WeightScale = 2^8 (exact; weights up to 255 in
 // magnitude) and the fp16 kernels multiply their accumulators by 2^-8 before the epilogue (exact as well).
+// The lower end of that: a weight below ~5e-4 (2^-11) has a subnormal lo part again, an absolute 2^-33 per weight -- a whole ROW of
+// such weights (a BatchNorm fold scale near zero) is accurate to 1e-6 of the tensor's scale but not of its own (include/kgdet_hip.h;
+// measured on the restated split by tests/test_dense_refs.py).
 constexpr float kF16WeightScale = 256.0f;
 // "Values beyond 65504 saturate" is made true by the MODE register's FP16_OVFL bit (bit 23: an overflowed FP16 VALU result
 // is clamped to +/-MAX_FP16, true infinities stay): set once at the top of every kernel that produces fp16 parts, no

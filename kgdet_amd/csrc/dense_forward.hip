@@ -812,7 +812,7 @@ int nn_ksplit(long long tiles, int stages) {
 // conv3x3_patch4 (3x3, stride 1) or conv_nn (everything else), the pixel tiling and the K split of one convolution: the
 // workspace query and the launch both read it from here
 struct NNPlan {
-  bool patch;
+  bool patch, halves;       // halves: conv3x3_patch4<2, 4>, a workgroup per 64-row half of a tile
   int TX, TY, NB, NW, tiles_x, n_nt, ks;
   long long tiles;
 };
@@ -872,7 +872,21 @@ NNPlan plan_nn(long long B, int M, int K, int H, int W, int taps, int stride) {
   }
   static const int force_ks = env_int("KGDET_CONV_KS", 0);
   if (force_ks > 0) p.ks = force_ks;
+  // conv3x3_patch4 with fewer than ~1.6 whole-tile workgroups per CU: 64-row halves (twice the workgroups) spread evenly over the
+  // CUs ... and M <= 64 (layer 1): the second half has no rows and leaves at once instead of multiplying zeros.  (The 160-pixel
+  // tiles have no half variant.)
+  static const int force_halves = env_int("KGDET_CONV_HALVES", -1);
+  p.halves = p.patch && p.NB == 4 &&
+             (force_halves >= 0 ? force_halves != 0 : ((p.ks == 1 && p.tiles > 256 && p.tiles < 400) || M <= 64));
   return p;
+}
+
+// which pass closes a launch of `ks` parts on HW output pixels per plane (kgdet_conv_apply_plan reports these numbers)
+enum NNCloser { kCloseStore = 0, kCloseSumEpilogue = 1, kCloseSumBiasAct = 2, kCloseSum = 3 };
+NNCloser nn_closer(int ks, long long HW, bool epilogue) {
+  if (ks <= 1) return kCloseStore;
+  if (!epilogue) return kCloseSum;
+  return HW % 2 == 0 ? kCloseSumEpilogue : kCloseSumBiasAct;
 }
 
 }  // namespace
@@ -945,6 +959,22 @@ extern "C" size_t kgdet_conv_apply_workspace_bytes(int64_t B, int32_t M, int32_t
   return ks > 1 ? (size_t)ks * B * M * HW * sizeof(float) : 0;
 }
 
+extern "C" int kgdet_conv_apply_plan(int64_t B, int32_t M, int32_t K, int32_t H, int32_t W, int32_t taps, int32_t stride,
+                                     int32_t out[KGDET_CONV_APPLY_PLAN_WORDS]) {
+  KGDET_CHECK_SHAPE(out, "null pointer");
+  KGDET_CHECK_SHAPE(B > 0 && M > 0 && K > 0 && H > 0 && W > 0 && (long long)H * W < (1LL << 30), "bad sizes");
+  KGDET_CHECK_SHAPE(taps == 1 || taps == 9, "taps must be 1 (1x1) or 9 (3x3)");
+  KGDET_CHECK_SHAPE(stride == 1 || stride == 2, "stride must be 1 or 2");
+  KGDET_CHECK_SHAPE(taps == 1 || K % kTK == 0, "reduction length %d is not a multiple of 16", K);
+  const NNPlan p = plan_nn(B, M, K, H, W, taps, stride);
+  KGDET_CHECK_SHAPE(p.tiles < (1LL << 28), "too many tiles");
+  const long long HW = (long long)((H + stride - 1) / stride) * ((W + stride - 1) / stride);
+  const int32_t words[KGDET_CONV_APPLY_PLAN_WORDS] = {
+      p.patch, p.TX, p.TY, p.NB, p.NW, p.ks, p.halves, (int32_t)p.tiles, p.n_nt, nn_closer(p.ks, HW, true), nn_closer(p.ks, HW, false)};
+  for (int i = 0; i < KGDET_CONV_APPLY_PLAN_WORDS; ++i) out[i] = words[i];
+  return KGDET_OK;
+}
+
 extern "C" int kgdet_conv_apply_epilogue_fmt(const void *packed, const float *x, float *y, const float *bias,
                                              const float *residual, int32_t relu, int64_t B, int32_t M, int32_t K,
                                              int32_t H, int32_t W, int32_t taps, int32_t stride, int32_t operand_format,
@@ -988,17 +1018,13 @@ extern "C" int kgdet_conv_apply_gated_fmt(const void *packed, const float *x, fl
   const int k_relu = ks > 1 ? 0 : relu;
   const unsigned char *img = (const unsigned char *)packed;
   if (plan.patch) {
-    // fewer than ~1.6 whole-tile workgroups per CU: 64-row halves (twice the workgroups) spread evenly over the CUs
-    static const int force_halves = env_int("KGDET_CONV_HALVES", -1);
-    // ... and M <= 64 (layer 1): the second half has no rows and leaves at once instead of multiplying zeros
-    const bool halves = force_halves >= 0 ? force_halves != 0 : ((ks == 1 && tiles > 256 && tiles < 400) || M <= 64);
     auto launch = [&](auto bf16_kernel, auto f16_kernel, unsigned g, unsigned threads) {
       launch_fmt(f16, bf16_kernel, f16_kernel, g, threads, stream, img, x, dst, M, K, H, W, n_mt, plan.tiles_x, n_nt, (int)tiles,
                  ks, part_stride, plan.TX, plan.TY, k_bias, k_residual, k_relu, k_gate);
     };
     if (plan.NB == 5)
       launch(conv3x3_patch4<4, 5, false>, conv3x3_patch4<4, 5, true>, grid, 256);
-    else if (halves)
+    else if (plan.halves)
       launch(conv3x3_patch4<2, 4, false>, conv3x3_patch4<2, 4, true>, (unsigned)((tiles * ks * 2 + 7) / 8) * 8, 128);
     else
       launch(conv3x3_patch4<4, 4, false>, conv3x3_patch4<4, 4, true>, grid, 256);
@@ -1019,7 +1045,8 @@ extern "C" int kgdet_conv_apply_gated_fmt(const void *packed, const float *x, fl
   KGDET_CHECK_LAUNCH("conv_nn");
   if (ks > 1) {
     const long long blocks = (part_stride / 2 + 255) / 256;
-    if ((bias || residual || relu || gate) && HW % 2 == 0)   // the epilogue in the sum's store
+    const NNCloser closer = nn_closer(ks, HW, bias || residual || relu || gate);
+    if (closer == kCloseSumEpilogue)   // the epilogue in the sum's store
       hipLaunchKernelGGL(conv1x1_sum_epilogue, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0,
                          (hipStream_t)stream, (const float *)workspace, y, part_stride, part_stride, ks, bias, residual, relu,
                          M, (long long)HW, gate);
@@ -1027,7 +1054,7 @@ extern "C" int kgdet_conv_apply_gated_fmt(const void *packed, const float *x, fl
       hipLaunchKernelGGL(conv1x1_sum, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, (hipStream_t)stream,
                          (const float *)workspace, y, part_stride, part_stride, ks);
     KGDET_CHECK_LAUNCH("conv1x1_sum");
-    if ((bias || residual || relu) && HW % 2 != 0) return kgdet_bias_act(y, bias, residual, B, M, HW, 0, relu, 0, stream);
+    if (closer == kCloseSumBiasAct) return kgdet_bias_act(y, bias, residual, B, M, HW, 0, relu, 0, stream);
   }
   return KGDET_OK;
 }

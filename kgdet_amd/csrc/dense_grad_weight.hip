@@ -782,6 +782,29 @@ extern "C" size_t kgdet_conv3x3_grad_weight_workspace_bytes(int64_t B, int32_t O
   return plan_gw(B, O, C, H, W, 9).bytes;
 }
 
+extern "C" int kgdet_conv_grad_weight_plan(int64_t B, int32_t O, int32_t C, int32_t H, int64_t W, int32_t taps,
+                                           int32_t out[KGDET_CONV_GRAD_WEIGHT_PLAN_WORDS]) {
+  // the checks of grad_weight() above (taps == 1: H = 1, W = the pixel count)
+  KGDET_CHECK_SHAPE(out, "null pointer");
+  KGDET_CHECK_SHAPE(taps == 1 || taps == 9, "taps must be 1 (1x1) or 9 (3x3)");
+  if (taps == 9) {
+    KGDET_CHECK_SHAPE(B > 0 && O > 0 && C > 0 && H > 0 && W > 0 && (long long)H * (W + 3) < (1LL << 23), "bad sizes");
+    if (C % kTN != 0) {
+      set_error("conv3x3_grad_weight needs C %% 128 == 0 (C=%d)", C);
+      return KGDET_E_UNSUPPORTED;
+    }
+  } else {
+    KGDET_CHECK_SHAPE(B > 0 && O > 0 && C > 0 && H == 1 && W > 0 && W < (1LL << 30), "bad sizes");
+  }
+  const GWPlan p = plan_gw(B, O, C, H, W, taps);
+  KGDET_CHECK_SHAPE(p.bytes < ((size_t)1 << 39), "workspace beyond what the report can express");
+  const int32_t words[KGDET_CONV_GRAD_WEIGHT_PLAN_WORDS] = {
+      p.use_ntp, p.padded, p.W % 4 == 0, p.splits, p.spi, p.per, 0, (int32_t)(p.copies_at >> 8), (int32_t)(p.rows_at >> 8),
+      p.tiles};
+  for (int i = 0; i < KGDET_CONV_GRAD_WEIGHT_PLAN_WORDS; ++i) out[i] = words[i];
+  return KGDET_OK;
+}
+
 extern "C" size_t kgdet_conv3x3_s2_grad_weight_workspace_bytes(int64_t B, int32_t O, int32_t C, int32_t H, int32_t W) {
   if (B <= 0 || O <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
   const long long HWo = (long long)((H + 1) / 2) * ((W + 1) / 2);
