@@ -826,6 +826,49 @@ int kgdet_coco_match(const int32_t *cells, const int64_t *sim_off, int32_t C, in
                      const double *sim, const double *d_area, const double *g_area, const uint8_t *g_ignore,
                      const int32_t *g_crowd, const double *area_rng, int32_t A, const double *best0, int32_t T,
                      int32_t *d_match, uint8_t *d_ignore, uint8_t *g_ignore_out, uint8_t *g_taken, void *stream);
+/* CocoEvaluator.accumulate on the device, from kgdet_coco_match's outputs as they lie in device memory (all pointers below
+ * are device pointers).  Results are BIT-EQUAL to evaluation_device.DeviceCocoEvaluator.accumulate_restatement: counts are
+ * int32, the two divisions are single float64 divisions without contraction, max and the comparisons are exact, and there
+ * are no float atomics, so two runs give the same bits.
+ * kgdet_coco_count_gt: n_gt int32 [K, A] = the number of ground truths g < NG with g_cat[g] == k (int32 [NG]) and
+ * g_ignore[g, a] == 0 (uint8 [NG, A], kgdet_coco_match's g_ignore_out).  Every element is written (NG == 0: zeros).
+ * kgdet_coco_accumulate: one workgroup per line (k, a, m, t) walks the category's sequence order[cat_cut[k] .. cat_cut[k+1])
+ * in tiles of KGDET_COCO_ACC_TILE positions.  order int64 [ND]: the detections grouped by category, inside a category in
+ * descending score, equal scores in (image, rank) order (ONE stable sort per evaluation); cat_cut int64 [K + 1]; rank int32
+ * [ND] = the detection's position inside its cell; a position is selected when rank < max_dets[m] (int32 [M], ascending).
+ * Over the selected positions tp counts d_match != 0 && !d_ignore and fp counts d_match == 0 && !d_ignore (int32 / uint8
+ * [ND, A, T]); score float64 [ND]; rec_thrs float64 [R].  Written, every element of them:
+ *   recall [T, K, A, M] = tp_total / n_gt; precision, scores [T, R, K, A, M]: with pos the first selected position where
+ *   tp / n_gt >= rec_thrs[r] (searchsorted side='left'), max over the positions >= pos of tp / (fp + tp + 2^-52) and the
+ *   score at pos; 0 where there is no such position (a line that selects nothing is all 0); all three -1 where
+ *   n_gt[k, a] == 0.
+ * An entry of order outside [0, ND) is skipped, cat_cut is clamped to [0, ND].
+ * workspace: 16 * tp_cap bytes per line, K * A * M * T lines (float64 precision and score at the first position of every
+ * true-positive count): workspace_bytes >= 16 * tp_cap * K * A * M * T, with tp_cap >= max over (k, a) of
+ * min(cat_cut[k+1] - cat_cut[k], n_gt[k, a]) -- kgdet_coco_match never yields more true positives than that (a regular
+ * ground truth is matched once); the host may take min(sequence length, ground truths of the category).  A line is
+ * recorded up to min(sequence length, n_gt, tp_cap) true positives; flags no matching could have written (more) are counted
+ * in recall and otherwise dropped, never stored out of bounds.
+ * Refused before any launch: A, T < 1 or A * T > 64, K, M, R < 1 or K * A * M * T >= 2^31, ND outside [0, 2^31 - 1),
+ * tp_cap < 0 (KGDET_E_SHAPE); a null pointer where data is required -- the detection arrays only when ND > 0, the workspace
+ * only when tp_cap > 0 (KGDET_E_SHAPE); a workspace that is too small (KGDET_E_WORKSPACE).
+ * kgdet_coco_pack_landmarks: kpt2json + load_results for landmark rows.  src float32 [n, 3K] (x, y, v per landmark);
+ * kxy float64 [n, K, 2] = np.round(float64(x | y), num_digits) = rint(v * 10^d) / 10^d (ties to even, two float64
+ * operations, no contraction); bbox float64 [n, 4] = (x0, y0, x1 - x0, y1 - y0) from the min / max over ALL K rounded
+ * coordinates, area float64 [n] = (x1 - x0) * (y1 - y0).  Bit-equal to the host packing (the sign of a zero extent
+ * corner follows the reduction order, as numpy's does).  One wave per row, KGDET_COCO_PACK_ROWS rows per workgroup, any n.
+ * n == 0 is a no-op; K < 1, n < 0 or n > 2^31 - 1 rows, num_digits outside [0, 15] or a null pointer: KGDET_E_SHAPE. */
+#define KGDET_COCO_ACC_TILE 1024
+#define KGDET_COCO_PACK_ROWS 4
+int kgdet_coco_count_gt(const uint8_t *g_ignore, const int32_t *g_cat, int64_t NG, int32_t K, int32_t A, int32_t *n_gt,
+                        void *stream);
+int kgdet_coco_accumulate(const int32_t *d_match, const uint8_t *d_ignore, const double *score, const int32_t *rank,
+                          const int64_t *order, const int64_t *cat_cut, const int32_t *n_gt, const int32_t *max_dets,
+                          const double *rec_thrs, int64_t ND, int32_t K, int32_t A, int32_t T, int32_t M, int32_t R,
+                          int64_t tp_cap, double *precision, double *recall, double *scores, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int kgdet_coco_pack_landmarks(const float *src, int64_t n, int32_t K, int32_t num_digits, double *kxy, double *bbox,
+                              double *area, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

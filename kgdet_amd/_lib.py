@@ -43,6 +43,8 @@ class AugSegment(ctypes.Structure):
 
 
 PREPROC_MAX_JOBS = 32   # KGDET_PREPROC_MAX_JOBS
+COCO_ACC_TILE = 1024    # KGDET_COCO_ACC_TILE: positions of a category's sequence per scan tile
+COCO_PACK_ROWS = 4      # KGDET_COCO_PACK_ROWS: landmark rows (waves) per workgroup
 
 
 class PreprocJob(ctypes.Structure):
@@ -91,6 +93,12 @@ def lib():
             L.kgdet_coco_similarity.restype = L.kgdet_coco_match.restype = ctypes.c_int
             L.kgdet_coco_similarity.argtypes = [i32, vp, vp, i32, i64, i64, i64] + [vp] * 8 + [i32, vp, vp]
             L.kgdet_coco_match.argtypes = [vp, vp, i32, i64, i64, i64] + [vp] * 6 + [i32, vp, i32] + [vp] * 5
+        if hasattr(L, 'kgdet_coco_accumulate'):
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_coco_count_gt.restype = L.kgdet_coco_accumulate.restype = L.kgdet_coco_pack_landmarks.restype = ctypes.c_int
+            L.kgdet_coco_count_gt.argtypes = [vp, vp, i64, i32, i32, vp, vp]
+            L.kgdet_coco_accumulate.argtypes = [vp] * 9 + [i64] + [i32] * 5 + [i64] + [vp] * 4 + [ctypes.c_size_t, vp]
+            L.kgdet_coco_pack_landmarks.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 

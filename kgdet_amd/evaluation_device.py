@@ -10,8 +10,11 @@ similarities and four nested Python loops for the matching.  This module keeps i
   ``single_gpu_test`` returns, no files: ``kpt2json``'s rounding applied to the arrays): detections sorted by cell, inside a
   cell by descending score (stable), cut to the type's ``max_dets[-1]``.
 * ``DeviceCocoEvaluator``: ``evaluate()`` runs similarity + matching for every cell in one launch each
-  (csrc/coco_eval.hip) or, with ``device='cpu'``, their numpy restatement below; ``accumulate()`` is numpy over the packed
+  (csrc/coco_eval.hip) or, with ``device='cpu'``, their numpy restatement below; ``accumulate()`` is one more launch over
+  the outputs where they lie on the device (csrc/coco_accumulate.hip) or ``accumulate_restatement()``, numpy over the packed
   outputs, vectorised per (category, area range, max_dets); ``summarize()`` is ``CocoEvaluator``'s.
+* ``pack_test_results(..., lazy_landmarks=True)``: the landmark rows stay float32 on the host and are rounded, with their
+  extents, by ``kgdet_coco_pack_landmarks`` chunk by chunk (``materialize`` is the numpy route).
 
 What the device computes differently from numpy is stated in DESIGN.md: box IoU is bit-identical; for OKS the exponent
 argument is bit-identical, ``exp`` and the order of the sum over the landmarks are the device's.
@@ -112,8 +115,10 @@ def _pack_dets(pg, kind, image_id, category_id, score, bbox, area, kxy, order=No
     else:
         order, ii, ci = order
     cell = ii[order] * len(pg.cat_ids) + ci[order]
+    if bbox is not None:                                            # (None: a lazy landmark Packed, see pack_test_results)
+        bbox, area = np.ascontiguousarray(bbox[order]), area[order]
     return Packed(kind=kind, cell=cell, start=_csr(cell, len(pg.img_ids) * len(pg.cat_ids)), img_idx=ii[order],
-                  cat_idx=ci[order], score=score[order], bbox=np.ascontiguousarray(bbox[order]), area=area[order],
+                  cat_idx=ci[order], score=score[order], bbox=bbox, area=area,
                   id=order.astype(np.int64) + 1, kxy=kxy)          # load_results: id = k + 1
 
 
@@ -228,11 +233,50 @@ def _landmarks_in_order(blocks, n, order, K, num_digits, batch=4096):
     return bbox, area, kxy
 
 
-def pack_test_results(packed_gt, dataset, results, num_digits=4):
+def _landmark_rows_in_order(blocks, n, order, K):
+    """the float32 landmark rows ``order`` keeps, copied straight into their packed place [len(order), 3K]: a gather, no
+    arithmetic and no float64 copy"""
+    pos = np.full(n, -1, np.int64)
+    pos[order] = np.arange(len(order))
+    out = np.zeros((len(order), 3 * K), np.float32)
+    r0 = 0
+    for blk in blocks:
+        if blk.dtype != np.float32:
+            raise TypeError('lazy_landmarks takes float32 landmark rows (what single_gpu_test returns), not %s' % blk.dtype)
+        to = pos[r0:r0 + len(blk)]
+        keep = to >= 0
+        out[to[keep]] = blk[keep]
+        r0 += len(blk)
+    return out
+
+
+def round_landmarks_restatement(values, num_digits):
+    """``kgdet_coco_pack_landmarks``'s rounding of float32 values: widen, ``rint(v * 10**d) / 10**d`` (ties to even, two
+    float64 operations).  Held to ``np.round(float64, d)`` bit for bit by tests/test_eval_accumulate_refs.py."""
+    v = np.asarray(values, dtype=np.float32).astype(np.float64)
+    scale = np.float64(10.0 ** num_digits)
+    return np.rint(v * scale) / scale
+
+
+def materialize(packed, num_digits=None):
+    """Fill ``kxy``, ``bbox`` and ``area`` of a lazy landmark Packed (``pack_test_results(..., lazy_landmarks=True)``) on the
+    host, by the numpy route of the eager packing: ``np.round(float64, num_digits)`` of the float32 rows, extents over all
+    coordinates.  A Packed that already holds them is returned as it is.  -> packed"""
+    if getattr(packed, 'kxy32', None) is None or (packed.kxy is not None and packed.bbox is not None):
+        return packed
+    a = np.round(packed.kxy32.astype(np.float64), packed.num_digits if num_digits is None else num_digits)
+    packed.bbox, packed.area, packed.kxy = _derive_from_landmarks(a)
+    return packed
+
+
+def pack_test_results(packed_gt, dataset, results, num_digits=4, lazy_landmarks=False):
     """{'bbox': packed[, 'keypoints': packed]} straight from what ``single_gpu_test`` / ``multi_gpu_test`` return, with the very
     numbers ``results2json`` + ``json.dump`` + ``load_results`` yield (a float's json text reads back as the same float):
     ``det2json`` for per-class box lists (no rounding), ``kpt2json`` for (boxes, scores, landmarks) tuples --
-    ``np.round(float64, num_digits)`` for the landmarks, Python's ``round`` for xywh and the score (``round_like_python``)."""
+    ``np.round(float64, num_digits)`` for the landmarks, Python's ``round`` for xywh and the score (``round_like_python``).
+    ``lazy_landmarks``: the 'keypoints' Packed carries ``kxy32`` -- the float32 rows [n, 3K] in packed order -- and
+    ``num_digits`` instead of ``kxy`` / ``bbox`` / ``area`` (None): ``DeviceCocoEvaluator.evaluate`` rounds them and takes the
+    extents on the GPU (``kgdet_coco_pack_landmarks``) and stores ``bbox`` / ``area``; ``materialize`` does it on the host."""
     if not isinstance(results[0], (list, tuple)):
         raise TypeError('invalid type of results')
     with_kpt = isinstance(results[0], tuple)
@@ -268,6 +312,11 @@ def pack_test_results(packed_gt, dataset, results, num_digits=4):
     out = dict(bbox=_pack_dets(packed_gt, 'bbox', img, cat, score, xywh, xywh[:, 2] * xywh[:, 3], None))
     if with_kpt:
         order = _order_dets(packed_gt, 'keypoints', img, cat, score)
+        if lazy_landmarks:
+            out['keypoints'] = _pack_dets(packed_gt, 'keypoints', img, cat, score, None, None, None, order=order)
+            out['keypoints'].kxy32 = _landmark_rows_in_order(kpts, len(rows), order[0], K)
+            out['keypoints'].num_digits = num_digits
+            return out
         bbox, area, kxy = _landmarks_in_order(kpts, len(rows), order[0], K, num_digits)
         out['keypoints'] = _pack_dets(packed_gt, 'keypoints', img, cat, score, bbox, area, kxy, order=order)
     return out
@@ -354,8 +403,12 @@ def _run_host(c, want_sim=True):
     return (sim if want_sim else None,) + match_restatement(c, sim)
 
 
-def _run_device(c, device, want_sim=True):
-    """the two launches of csrc/coco_eval.hip for one chunk; the similarity matrix stays on the device between them"""
+def _run_device(c, device, want_sim=True, on_device=None):
+    """the two launches of csrc/coco_eval.hip for one chunk; the similarity matrix stays on the device between them.  A lazy
+    landmark chunk (``c.kxy32``) first runs ``kgdet_coco_pack_landmarks`` on its float32 rows: the two kernels read its
+    ``d_kxy`` / ``d_area`` in device memory, ``bbox`` / ``area`` come back as ``c.out_bbox`` / ``c.out_area``.  ``on_device``:
+    (d_match, d_ignore, g_ignore) dataset-sized device tensors -- the chunk writes its slices there, ``g0`` is added on the
+    device and the three are not downloaded (None in their place)."""
     import torch
     from . import _lib
     L = _lib.lib()
@@ -372,17 +425,33 @@ def _run_device(c, device, want_sim=True):
     with torch.cuda.device(dev):
         cells, sim_off = up(c.cells, np.int32), up(c.sim_off, np.int64)
         d_box, g_box = (None if kp else up(c.d_box)), up(c.g_box)
-        d_kxy, g_kpt = (up(c.d_kxy), up(c.g_kpt)) if kp else (None, None)
-        d_area, g_area = up(c.d_area), up(c.g_area)
+        stream, p = _lib.current_stream(), _lib.ptr
+        i32, i64 = ctypes.c_int32, ctypes.c_int64
+        if kp and getattr(c, 'kxy32', None) is not None:
+            K = c.kxy32.shape[1] // 3
+            src = up(c.kxy32)
+            d_kxy = torch.empty((c.nd, K, 2), dtype=torch.float64, device=dev)
+            d_bbox = torch.empty((c.nd, 4), dtype=torch.float64, device=dev)
+            d_area = torch.empty((c.nd,), dtype=torch.float64, device=dev)
+            _lib.check(L.kgdet_coco_pack_landmarks(p(src), i64(c.nd), i32(K), i32(c.num_digits), p(d_kxy), p(d_bbox), p(d_area),
+                                                   stream), 'kgdet_coco_pack_landmarks')
+            c.out_bbox, c.out_area = d_bbox.cpu().numpy(), d_area.cpu().numpy()
+            del src
+            g_kpt = up(c.g_kpt)
+        else:
+            d_kxy, g_kpt = (up(c.d_kxy), up(c.g_kpt)) if kp else (None, None)
+            d_area = up(c.d_area)
+        g_area = up(c.g_area)
         g_crowd, g_nvis, g_ign = up(c.g_crowd, np.int32), up(c.g_nvis, np.int32), up(c.g_ign, np.uint8)
         var, rng, best0 = up(c.var), up(c.area_rng), up(c.best0)
         sim = torch.zeros(max(c.sim_size, 1), dtype=torch.float64, device=dev)
-        d_match = torch.zeros((c.nd, A, T), dtype=torch.int32, device=dev)
-        d_ignore = torch.zeros((c.nd, A, T), dtype=torch.uint8, device=dev)
-        g_ignore = torch.zeros((c.ng, A), dtype=torch.uint8, device=dev)
+        if on_device is None:
+            d_match = torch.zeros((c.nd, A, T), dtype=torch.int32, device=dev)
+            d_ignore = torch.zeros((c.nd, A, T), dtype=torch.uint8, device=dev)
+            g_ignore = torch.zeros((c.ng, A), dtype=torch.uint8, device=dev)
+        else:
+            d_match, d_ignore, g_ignore = on_device[0][c.d0:c.d1], on_device[1][c.d0:c.d1], on_device[2][c.g0:c.g1]
         g_taken = torch.empty((c.ng, A, T), dtype=torch.uint8, device=dev)
-        stream, p = _lib.current_stream(), _lib.ptr
-        i32, i64 = ctypes.c_int32, ctypes.c_int64
         C = len(c.cells)
         _lib.check(L.kgdet_coco_similarity(i32(1 if kp else 0), p(cells), p(sim_off), i32(C), i64(c.nd), i64(c.ng),
                                            i64(c.sim_size), p(d_box), p(d_kxy), p(g_box), p(g_kpt), p(g_area), p(g_crowd),
@@ -390,6 +459,10 @@ def _run_device(c, device, want_sim=True):
         _lib.check(L.kgdet_coco_match(p(cells), p(sim_off), i32(C), i64(c.nd), i64(c.ng), i64(c.sim_size), p(sim), p(d_area),
                                       p(g_area), p(g_ign), p(g_crowd), p(rng), i32(A), p(best0), i32(T), p(d_match),
                                       p(d_ignore), p(g_ignore), p(g_taken), stream), 'kgdet_coco_match')
+        if on_device is not None:
+            if c.g0:
+                d_match.add_((d_match > 0).to(torch.int32), alpha=c.g0)       # chunk-local -> packed index
+            return sim[:c.sim_size].cpu().numpy() if want_sim else None, None, None, None
         return (sim[:c.sim_size].cpu().numpy() if want_sim else None, d_match.cpu().numpy(), d_ignore.cpu().numpy(),
                 g_ignore.cpu().numpy())
 
@@ -405,6 +478,36 @@ def _default_device():
     return 'cpu'
 
 
+def category_order(packed_dt, K):
+    """(order int64 [ND], cat_cut int64 [K + 1]): the detections grouped by category, inside a category in descending score,
+    equal scores in packed = (image, rank) order -- ONE stable sort per evaluation.  Restricted to ``rank < max_det`` it is the
+    stable score sort of that subset, i.e. the per-``max_dets`` argsort of ``accumulate_restatement``."""
+    d = packed_dt
+    order = np.lexsort((-d.score, d.cat_idx)).astype(np.int64)          # (stable: ties keep the packed order)
+    return order, np.searchsorted(d.cat_idx[order], np.arange(K + 1)).astype(np.int64)
+
+
+def _has_device_accumulate():
+    from . import _lib
+    return hasattr(_lib.lib(), 'kgdet_coco_accumulate')
+
+
+class _DeviceOutputs(object):
+    """``evaluate()``'s outputs while they stay in device memory (``dev`` = d_match, d_ignore, g_ignore tensors): the host
+    arrays of the same names are downloaded when first asked for, and kept"""
+
+    def __init__(self, dev, **kw):
+        self.dev = dev
+        self.__dict__.update(kw)
+
+    def __getattr__(self, name):                  # (only reached for what is not there yet)
+        if name not in ('d_match', 'd_ignore', 'g_ignore'):
+            raise AttributeError(name)
+        self.d_match, self.g_ignore = self.dev[0].cpu().numpy(), self.dev[2].cpu().numpy()
+        self.d_ignore = self.dev[1].cpu().numpy().view(bool)
+        return self.__dict__[name]
+
+
 class DeviceCocoEvaluator(CocoEvaluator):
     """``CocoEvaluator`` on packed arrays.  ``device``: a CUDA device (the HIP kernels), ``'cpu'`` (their numpy restatement)
     or None = the GPU when there is one and the library is built, else the restatement.  ``params`` as ``CocoEvaluator``'s;
@@ -412,10 +515,15 @@ class DeviceCocoEvaluator(CocoEvaluator):
     not the packed ground truth's (pack a subset instead), when ``max_dets[-1]`` is not the cut the detections were packed
     with, and for ``use_cats = 0``.  ``iou_thrs``, ``rec_thrs``, ``area_rng`` (at most 64 (range, threshold) pairs) and the
     smaller ``max_dets`` entries are honoured.  ``keep_similarity``: also download the similarity matrices (``similarity``);
-    the stats do not need them."""
+    the stats do not need them.  ``device_accumulate``: keep the matching outputs in device memory and run ``accumulate`` as
+    ``kgdet_coco_accumulate`` (bit-equal to ``accumulate_restatement``); None = on for a CUDA device when the library has the
+    kernel, else off; True on the CPU path, or without the kernel, is an error.  A lazy landmark Packed
+    (``pack_test_results(..., lazy_landmarks=True)``) is rounded on the GPU chunk by chunk, or on the host for ``'cpu'``;
+    ``evaluate`` stores its ``bbox`` / ``area``."""
 
-    def __init__(self, packed_gt, packed_dt, iou_type, device=None, keep_similarity=False):
+    def __init__(self, packed_gt, packed_dt, iou_type, device=None, keep_similarity=False, device_accumulate=None):
         self.keep_similarity = keep_similarity
+        self.device_accumulate = device_accumulate
         self.params = EvalParams(iou_type)
         if len(packed_dt.score) and packed_dt.kind != iou_type:
             raise ValueError('the detections were packed as %r results (sorted and cut for that type), not %r'
@@ -439,6 +547,9 @@ class DeviceCocoEvaluator(CocoEvaluator):
         common = dict(iou_type=p.iou_type, var=(landmark_meta()['oks_sigmas'] * 2) ** 2,
                       area_rng=np.asarray(p.area_rng, dtype=np.float64).reshape(-1, 2),
                       best0=np.minimum(np.asarray(p.iou_thrs, dtype=np.float64), 1 - 1e-10))
+        lazy = kp and d.kxy is None and getattr(d, 'kxy32', None) is not None      # (rounded by the chunk on the device)
+        if lazy:
+            common['num_digits'] = d.num_digits
         lo = 0
         while lo < len(cells):
             hi = int(np.searchsorted(cells[:, 0] + cells[:, 1], cells[lo, 0] + limit, side='right'))
@@ -449,7 +560,9 @@ class DeviceCocoEvaluator(CocoEvaluator):
             size = local[:, 1] * local[:, 3]
             yield Packed(d0=d0, d1=d1, g0=g0, g1=g1, nd=d1 - d0, ng=g1 - g0, cells=local,
                          sim_off=np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64), sim_size=int(size.sum()),
-                         d_box=d.bbox[d0:d1], d_area=d.area[d0:d1], d_kxy=(d.kxy[d0:d1] if d.kxy is not None else np.zeros((0, g.num_landmarks, 2))) if kp else None,
+                         kxy32=d.kxy32[d0:d1] if lazy else None,
+                         d_box=None if lazy else d.bbox[d0:d1], d_area=None if lazy else d.area[d0:d1],
+                         d_kxy=(d.kxy[d0:d1] if d.kxy is not None else np.zeros((0, g.num_landmarks, 2))) if kp and not lazy else None,
                          g_box=g.bbox[g0:g1], g_area=g.area[g0:g1], g_kpt=g.keypoints[g0:g1] if kp else None,
                          g_crowd=g.iscrowd[g0:g1], g_nvis=g.num_visible[g0:g1], g_ign=base[g0:g1].astype(np.uint8), **common)
             lo = hi
@@ -458,8 +571,16 @@ class DeviceCocoEvaluator(CocoEvaluator):
         p = self.params
         if not p.use_cats:
             raise ValueError('use_cats = 0 is not offered on the packed path: use evaluation.CocoEvaluator')
-        if p.iou_type == 'keypoints' and len(self.dt.score) and self.dt.kxy is None:
+        on_cpu = str(self.device) == 'cpu'
+        if on_cpu and p.iou_type == 'keypoints':
+            materialize(self.dt)                                    # (a lazy Packed: the numpy route)
+        if p.iou_type == 'keypoints' and len(self.dt.score) and self.dt.kxy is None and getattr(self.dt, 'kxy32', None) is None:
             raise ValueError('landmark evaluation needs landmark detections')
+        dev_acc = self.device_accumulate
+        if dev_acc is None:
+            dev_acc = not on_cpu and _has_device_accumulate()
+        elif dev_acc and (on_cpu or not _has_device_accumulate()):
+            raise ValueError('device_accumulate needs a CUDA device and a library with kgdet_coco_accumulate')
         if (not np.array_equal(np.unique(p.img_ids), self.gt.img_ids) or not np.array_equal(np.unique(p.cat_ids), self.gt.cat_ids)):
             raise ValueError('params.img_ids / cat_ids differ from the packed ground truth: the cells are fixed by packing '
                              '(pack the subset, or use evaluation.CocoEvaluator)')
@@ -471,9 +592,28 @@ class DeviceCocoEvaluator(CocoEvaluator):
         nd, ng = len(self.dt.score), len(self.gt.id)
         d_match = d_ignore = g_ignore = None
         sims = []
-        run = _run_host if str(self.device) == 'cpu' else (lambda c, want: _run_device(c, self.device, want))
+        lazy = p.iou_type == 'keypoints' and self.dt.kxy is None and getattr(self.dt, 'kxy32', None) is not None
+        if lazy:
+            self.dt.bbox, self.dt.area = np.zeros((nd, 4)), np.zeros(nd)
+        size = np.diff(self.dt.start) * np.diff(self.gt.start)
+        sim_start = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+        if dev_acc:
+            import torch
+            dev = torch.device(self.device)
+            on_device = (torch.zeros((nd, A, T), dtype=torch.int32, device=dev), torch.zeros((nd, A, T), dtype=torch.uint8, device=dev),
+                         torch.zeros((ng, A), dtype=torch.uint8, device=dev))
+            for c in self._chunks(CHUNK_DETS[p.iou_type]):
+                sims.append(_run_device(c, self.device, self.keep_similarity, on_device)[0])
+                if lazy:
+                    self.dt.bbox[c.d0:c.d1], self.dt.area[c.d0:c.d1] = c.out_bbox, c.out_area
+            self._out = _DeviceOutputs(on_device, sim_start=sim_start,
+                                       sim=(np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None)
+            return self
+        run = _run_host if on_cpu else (lambda c, want: _run_device(c, self.device, want))
         for c in self._chunks(CHUNK_DETS[p.iou_type]):
             sim, dm, di, gi = run(c, self.keep_similarity)
+            if lazy:
+                self.dt.bbox[c.d0:c.d1], self.dt.area[c.d0:c.d1] = c.out_bbox, c.out_area
             if c.g0:
                 np.add(dm, c.g0, out=dm, where=dm > 0)             # chunk-local -> packed index, in place
             if c.nd == nd and c.ng == ng:
@@ -486,10 +626,9 @@ class DeviceCocoEvaluator(CocoEvaluator):
             sims.append(sim)
         if d_match is None:
             d_match, d_ignore, g_ignore = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8), np.zeros((ng, A), np.uint8)
-        size = np.diff(self.dt.start) * np.diff(self.gt.start)
         self._out = Packed(d_match=d_match, d_ignore=d_ignore.view(bool), g_ignore=g_ignore,
                            sim=(np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None,
-                           sim_start=np.concatenate([[0], np.cumsum(size)]).astype(np.int64))
+                           sim_start=sim_start)
         return self
 
     # --- accessors at the level of CocoEvaluator's intermediate results -----------------------------
@@ -526,6 +665,51 @@ class DeviceCocoEvaluator(CocoEvaluator):
 
     # --- accumulate ---------------------------------------------------------------------------------
     def accumulate(self):
+        """``CocoEvaluator.accumulate``.  When ``evaluate()`` kept its outputs on the device (``device_accumulate``):
+        ``kgdet_coco_accumulate`` -- ``order`` / ``cat_cut`` are built on the host by ONE numpy lexsort (``category_order``;
+        the sort is not the hot path), ``n_gt`` by ``kgdet_coco_count_gt``, and only precision, recall and scores are
+        downloaded, bit-equal to ``accumulate_restatement``.  Otherwise ``accumulate_restatement`` itself."""
+        if self._out is None:
+            raise RuntimeError('Please run evaluate() first')
+        if not isinstance(self._out, _DeviceOutputs):
+            return self.accumulate_restatement()
+        import torch
+        from . import _lib
+        L = _lib.lib()
+        p, d, g = self.params, self.dt, self.gt
+        T, R, K, A, M = len(p.iou_thrs), len(p.rec_thrs), len(p.cat_ids), len(p.area_rng), len(p.max_dets)
+        nd, ng = len(d.score), len(g.id)
+        if min(T, R, K, A, M) == 0:
+            return self.accumulate_restatement()                    # (empty result arrays: nothing to launch)
+        dev = self._out.dev[0].device
+        order, cat_cut = category_order(d, K)
+        rank = (np.arange(nd) - d.start[d.cell]) if nd else np.zeros(0, np.int64)
+        tp_cap = int(np.minimum(np.diff(cat_cut), np.bincount(g.cat_idx, minlength=K)[:K]).max())
+
+        def up(a, dtype):
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dtype, copy=False))).to(dev)
+
+        with torch.cuda.device(dev):
+            d_match, d_ignore, g_ignore = self._out.dev
+            stream, ptr = _lib.current_stream(), _lib.ptr
+            i32, i64 = ctypes.c_int32, ctypes.c_int64
+            n_gt = torch.empty((K, A), dtype=torch.int32, device=dev)
+            _lib.check(L.kgdet_coco_count_gt(ptr(g_ignore), ptr(up(g.cat_idx, np.int32)), i64(ng), i32(K), i32(A), ptr(n_gt),
+                                             stream), 'kgdet_coco_count_gt')
+            precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+            scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+            recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+            work = torch.empty(2 * tp_cap * K * A * M * T, dtype=torch.float64, device=dev)
+            args = [up(d.score, np.float64), up(rank, np.int32), up(order, np.int64), up(cat_cut, np.int64), n_gt,
+                    up(p.max_dets, np.int32), up(p.rec_thrs, np.float64)]
+            _lib.check(L.kgdet_coco_accumulate(ptr(d_match), ptr(d_ignore), *[ptr(a) for a in args], i64(nd), i32(K), i32(A),
+                                               i32(T), i32(M), i32(R), i64(tp_cap), ptr(precision), ptr(recall), ptr(scores),
+                                               ptr(work), ctypes.c_size_t(work.numel() * 8), stream), 'kgdet_coco_accumulate')
+            self.eval = dict(counts=[T, R, K, A, M], precision=precision.cpu().numpy(), recall=recall.cpu().numpy(),
+                             scores=scores.cpu().numpy())
+        return self
+
+    def accumulate_restatement(self):
         """``CocoEvaluator.accumulate`` on the packed outputs: per (category, area range, max_dets) one stable score sort, integer
         cumulative sums over all thresholds at once, the precision envelope and ``searchsorted(side='left')`` per threshold."""
         if self._out is None:
@@ -571,23 +755,27 @@ class DeviceCocoEvaluator(CocoEvaluator):
         return self
 
 
-def evaluate_packed(packed_gt, packed_dt, iou_type, device=None, verbose=False):
-    return DeviceCocoEvaluator(packed_gt, packed_dt, iou_type, device).evaluate().accumulate().summarize(verbose)
+def evaluate_packed(packed_gt, packed_dt, iou_type, device=None, verbose=False, device_accumulate=None):
+    return DeviceCocoEvaluator(packed_gt, packed_dt, iou_type, device,
+                               device_accumulate=device_accumulate).evaluate().accumulate().summarize(verbose)
 
 
-def evaluate_results(dataset, results, result_types=('bbox', 'keypoints'), device=None, packed_gt=None, verbose=False):
+def evaluate_results(dataset, results, result_types=('bbox', 'keypoints'), device=None, packed_gt=None, verbose=False,
+                     lazy_landmarks=None, device_accumulate=None):
     """{type: stats} for what ``single_gpu_test`` / ``multi_gpu_test`` returned for ``dataset``, without result files: the
     numbers of ``coco_eval(results2json(dataset, results, ...), result_types, dataset.coco)``.  ``packed_gt``: the dataset's
-    ``pack_ground_truth(dataset.coco)`` when the caller keeps it between calls (a validation hook does)."""
+    ``pack_ground_truth(dataset.coco)`` when the caller keeps it between calls (a validation hook does).  ``lazy_landmarks``
+    (None = off): the landmark rows stay float32 on the host and are rounded on the device (``pack_test_results``);
+    ``device_accumulate``: ``DeviceCocoEvaluator``'s."""
     for t in result_types:
         if t not in ('bbox', 'keypoints'):
             raise ValueError('unsupported result type {!r}'.format(t))
     if packed_gt is None:
         packed_gt = pack_ground_truth(dataset.coco)
-    packed = pack_test_results(packed_gt, dataset, results)
+    packed = pack_test_results(packed_gt, dataset, results, lazy_landmarks=bool(lazy_landmarks))
     out = {}
     for t in result_types:
         if t not in packed:
             raise ValueError('the results hold no {!r} detections'.format(t))
-        out[t] = evaluate_packed(packed_gt, packed[t], t, device, verbose)
+        out[t] = evaluate_packed(packed_gt, packed[t], t, device, verbose, device_accumulate)
     return out

@@ -419,7 +419,8 @@ class Runner(object):
     def __init__(self, model, optimizer, work_dir=None, lr_config=None, optimizer_config=None, checkpoint_config=None,
                  log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None):
         """``eval_config = dict(dataset=..., interval=1, imgs_per_gpu=1, device_preprocess=False, group=None, to_device=None,
-        result_types=('bbox', 'keypoints'), device=None)``: validation after every ``interval``-th epoch (``validate``)."""
+        result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None)``: validation after every
+        ``interval``-th epoch (``validate``); the last two are ``evaluation_device.evaluate_results``'s."""
         self.model, self.optimizer, self.work_dir = model, optimizer, work_dir
         self.eval_config = dict(eval_config) if eval_config else None
         self._packed_gt = None
@@ -547,7 +548,8 @@ class Runner(object):
             device = next(self.model.parameters()).device
         types = [t for t in cfg.get('result_types', ('bbox', 'keypoints'))
                  if t == 'bbox' or isinstance(results[0], tuple)]
-        stats = evd.evaluate_results(dataset, results, types, device=device, packed_gt=self._packed_gt)
+        stats = evd.evaluate_results(dataset, results, types, device=device, packed_gt=self._packed_gt,
+                                     lazy_landmarks=cfg.get('lazy_landmarks'), device_accumulate=cfg.get('device_accumulate'))
         rec = OrderedDict(epoch=self.epoch)
         for t in types:
             names = ['mAP', 'mAP_50', 'mAP_75', 'mAP_s', 'mAP_m', 'mAP_l']

@@ -1,6 +1,7 @@
 """Time the packed (device) evaluator against evaluation.CocoEvaluator on the same detections.
 
     python tools/time_eval.py [--images N] [--dets P] [--device cuda|cpu] [--types bbox,keypoints] [--no-host]
+                              [--lazy-landmarks] [--device-accumulate]
 
 A validation set of N images is built from the committed demo annotations (tests/golden/demo_dataset-32.json replicated
 under fresh image / annotation ids); every image gets P detections in the form ``single_gpu_test`` returns them (per class
@@ -9,7 +10,10 @@ categories and scores (seeded).  Device route, as the validation hook runs it: `
 then per type ``evaluate`` (upload, similarity + matching, download) and ``accumulate``.  Host route, as ``coco_eval`` runs it
 minus the file: ``kpt2json``, then per type ``load_results``, ``CocoEvaluator.evaluate``, ``accumulate``.  The ``stats`` must
 be equal.  ``--no-host`` leaves the host route out (it holds every detection as a dict of Python floats: about 30 kB per
-landmark detection).  Prints one JSON line with seconds per stage, totals, milliseconds per image and host / device ratios."""
+landmark detection).  ``--lazy-landmarks`` / ``--device-accumulate`` (a CUDA device): the device route is run a second time
+with the landmark rounding (``kgdet_coco_pack_landmarks``) and / or ``accumulate`` (``kgdet_coco_accumulate``) on the GPU and
+reported as ``device_route``; the first run, with both off, becomes ``old_route``, and the ``stats`` of the two must be equal.
+Prints one JSON line with seconds per stage, totals, milliseconds per image and host / device ratios."""
 import argparse
 import json
 import os
@@ -99,6 +103,8 @@ def main():
     ap.add_argument('--device', default=None)
     ap.add_argument('--types', default='bbox,keypoints')
     ap.add_argument('--no-host', action='store_true')
+    ap.add_argument('--lazy-landmarks', action='store_true')
+    ap.add_argument('--device-accumulate', action='store_true')
     args = ap.parse_args()
     device = args.device or evd._default_device()
     types = args.types.split(',')
@@ -112,21 +118,37 @@ def main():
     packed_gt = evd.pack_ground_truth(index)
     out['pack_ground_truth_s'] = round(clock() - t0, 4)
     evd.evaluate_packed(packed_gt, evd.pack_results(packed_gt, []), 'bbox', device)     # context, library load, first launches
-    dev = dict()
-    t0 = clock()
-    packed = evd.pack_test_results(packed_gt, data, results)
-    dev['pack_s'] = clock() - t0
-    got = {}
-    for typ in types:
+
+    def device_route(lazy, dev_acc):
+        if dev_acc:
+            import torch
+        dev = dict()
         t0 = clock()
-        e = evd.DeviceCocoEvaluator(packed_gt, packed[typ], typ, device=device).evaluate()
-        t1 = clock()
-        e.accumulate()
-        t2 = clock()
-        got[typ] = e.summarize(verbose=False)
-        dev[typ] = dict(kept_detections=int(len(packed[typ].score)), match_s=t1 - t0, accumulate_s=t2 - t1)
-    dev['total_s'] = dev['pack_s'] + sum(dev[t]['match_s'] + dev[t]['accumulate_s'] for t in types)
-    dev['ms_per_image'] = 1e3 * dev['total_s'] / args.images
+        packed = evd.pack_test_results(packed_gt, data, results, lazy_landmarks=lazy)
+        dev['pack_s'] = clock() - t0
+        got = {}
+        for typ in types:
+            t0 = clock()
+            e = evd.DeviceCocoEvaluator(packed_gt, packed[typ], typ, device=device, device_accumulate=dev_acc).evaluate()
+            if dev_acc:
+                torch.cuda.synchronize()                            # (nothing is downloaded here: wait for the launches)
+            t1 = clock()
+            e.accumulate()
+            t2 = clock()
+            got[typ] = e.summarize(verbose=False)
+            dev[typ] = dict(kept_detections=int(len(packed[typ].score)), match_s=t1 - t0, accumulate_s=t2 - t1)
+        dev['total_s'] = dev['pack_s'] + sum(dev[t]['match_s'] + dev[t]['accumulate_s'] for t in types)
+        dev['ms_per_image'] = 1e3 * dev['total_s'] / args.images
+        return dev, got
+
+    dev, got = device_route(False, False)                      # the route with packing and accumulate on the host
+    if args.lazy_landmarks or args.device_accumulate:
+        out['old_route'] = dev
+        dev, new = device_route(args.lazy_landmarks, args.device_accumulate)
+        dev['lazy_landmarks'], dev['device_accumulate'] = args.lazy_landmarks, args.device_accumulate
+        for typ in types:
+            assert np.array_equal(new[typ], got[typ]), (typ, new[typ], got[typ])
+        out['ratio_old_new'] = out['old_route']['total_s'] / dev['total_s']
     out['device_route'] = dev
     if not args.no_host:
         host = dict()
