@@ -869,6 +869,55 @@ int kgdet_coco_accumulate(const int32_t *d_match, const uint8_t *d_ignore, const
                           size_t workspace_bytes, void *stream);
 int kgdet_coco_pack_landmarks(const float *src, int64_t n, int32_t K, int32_t num_digits, double *kxy, double *bbox,
                               double *area, void *stream);
+/* pack_test_results on the device: the detections of a test run as they lie in rows float32 [N, M, W], W = 7 + 3K (the
+ * layout of get_bboxes_packed_tensor: box x1 y1 x2 y2, score, label, count, K landmarks x y v; runner.DeviceResults.rows),
+ * ordered, rounded, cut and gathered into the packed arrays of evaluation_device.Packed for BOTH result kinds, bit-equal to
+ * evaluation_device.pack_rows_restatement and so to pack_test_results(..., lazy_landmarks=True) on the host list.  All
+ * pointers are device pointers except the two kgdet_coco_packed_dets structs themselves (host; their members are device
+ * pointers).  rows needs 4-byte alignment only; kxy32 8-byte alignment.  Of image n only the first count rows are read,
+ * count = trunc(rows[n, 0, 6]); a label is trunc(rows[n, i, 5]), rows whose label lies outside [0, L) are dropped as
+ * bbox2result_kp drops them.
+ * kgdet_coco_order_dets (one workgroup per image):  img_slot int32 [N] = the image's index into the packed ground truth's
+ * sorted image ids (-1: unknown), cat_of_label int32 [L] = the label's index into its sorted category ids in [0, C) or -1
+ * (such a row is never packed, but counts in the ids), n_cells = images of the ground truth x C.  Per row i < count with a
+ * label in range it writes vals float64 [N, M, 6] = x, y, w, h, score, area: xywh = x1, y1, x2 - x1 + 1, y2 - y1 + 1 on the
+ * widened values, xywh and the score rounded like Python's round(v, num_digits) -- with S = 10^d: p = |v| * S,
+ * e = fma(|v|, S, -p), n = floor(p) or floor(p) + 1 by p - floor(p) against one half, at one half by the sign of e, at
+ * e == 0 the even one; copysign(n / S, v) -- and area = w * h of the rounded values; and info int32 [N, M, 3] = the
+ * category index or -1, k = the row's index in the image's enumeration (label ascending, then row order), and the rank inside
+ * the (image, category) cell by descending rounded score, ties by k (-1, -1, -1 for a dropped row).  img_rows int32 [N] = the
+ * rows of the image that count in the ids; cnt_bbox / cnt_kp int32 [n_cells]: min(rows of the cell, cut) at
+ * [img_slot * C + c] for every c < C of every image with a known slot (cells of other images are not touched: zero them).
+ * flags int32 [2], ADDED to (zero them): [0] values that are not finite or with |v| * 10^d >= 2^40, left unrounded;
+ * [1] images whose count is not in [0, M] or that hold rows but no known slot (skipped), and, from the scatter, rows whose
+ * place lies outside the output (skipped).  The caller reads the flags with the counts and treats non-zero as an error.
+ * kgdet_coco_scatter_dets (one workgroup per image):  img_base int64 [N] = exclusive scan of img_rows in image order,
+ * start_bbox / start_kp int64 [n_cells + 1] = exclusive scans of cnt_bbox / cnt_kp.  A row with rank < cut goes to
+ * pos = start[cell] + rank of that kind: cell = img_slot * C + category, img_idx, cat_idx, id = img_base + k + 1 (int64
+ * [n]), score [n], bbox [n, 4], area [n] (float64; bbox and area may be NULL: not written), and for out_kp kxy32 float32
+ * [n, 3K] = the row's landmark columns (NULL: not gathered), one wave per row, 16-byte loads at the source's 4-byte
+ * alignment and 8-byte stores (K even; 4-byte accesses for odd K).  Every element of the outputs is written when start and
+ * n come from the order kernel's counts.
+ * Refused before any launch (KGDET_E_SHAPE): num_digits outside [1, 9], M outside [1, KGDET_COCO_ORDER_MAX_ROWS], L outside
+ * [1, KGDET_COCO_ORDER_MAX_LABELS], W != 7 + 3K with K >= 1, C outside [1, 32767], a negative size or cut, N >= 2^31, a
+ * null pointer where data is required.  N == 0 is a no-op. */
+#define KGDET_COCO_ORDER_MAX_ROWS 1024
+#define KGDET_COCO_ORDER_MAX_LABELS 64
+typedef struct {
+  int64_t n;                               /* rows of the packed arrays */
+  int64_t *cell, *img_idx, *cat_idx, *id;  /* [n] */
+  double *score, *bbox, *area;             /* [n], [n, 4], [n]; bbox / area may be NULL */
+  float *kxy32;                            /* [n, 3K] or NULL */
+} kgdet_coco_packed_dets;
+int kgdet_coco_order_dets(const float *rows, int64_t N, int32_t M, int32_t W, const int32_t *img_slot,
+                          const int32_t *cat_of_label, int32_t L, int32_t C, int64_t n_cells, int32_t num_digits,
+                          int32_t cut_bbox, int32_t cut_kp, double *vals, int32_t *info, int32_t *img_rows, int32_t *cnt_bbox,
+                          int32_t *cnt_kp, int32_t *flags, void *stream);
+int kgdet_coco_scatter_dets(const float *rows, int64_t N, int32_t M, int32_t W, const int32_t *img_slot, int32_t C,
+                            int64_t n_cells, const double *vals, const int32_t *info, const int64_t *img_base,
+                            const int64_t *start_bbox, const int64_t *start_kp, int32_t cut_bbox, int32_t cut_kp,
+                            const kgdet_coco_packed_dets *out_bbox, const kgdet_coco_packed_dets *out_kp, int32_t *flags,
+                            void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

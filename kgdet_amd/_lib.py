@@ -45,6 +45,14 @@ class AugSegment(ctypes.Structure):
 PREPROC_MAX_JOBS = 32   # KGDET_PREPROC_MAX_JOBS
 COCO_ACC_TILE = 1024    # KGDET_COCO_ACC_TILE: positions of a category's sequence per scan tile
 COCO_PACK_ROWS = 4      # KGDET_COCO_PACK_ROWS: landmark rows (waves) per workgroup
+COCO_ORDER_MAX_ROWS = 1024    # KGDET_COCO_ORDER_MAX_ROWS: detections per image kgdet_coco_order_dets ranks in LDS
+COCO_ORDER_MAX_LABELS = 64    # KGDET_COCO_ORDER_MAX_LABELS
+
+
+class CocoPackedDets(ctypes.Structure):
+    """kgdet_coco_packed_dets (the packed arrays of one result kind, device pointers)"""
+    _fields_ = [('n', ctypes.c_int64)] + [(n, ctypes.c_void_p) for n in (
+        'cell', 'img_idx', 'cat_idx', 'id', 'score', 'bbox', 'area', 'kxy32')]
 
 
 class PreprocJob(ctypes.Structure):
@@ -99,6 +107,12 @@ def lib():
             L.kgdet_coco_count_gt.argtypes = [vp, vp, i64, i32, i32, vp, vp]
             L.kgdet_coco_accumulate.argtypes = [vp] * 9 + [i64] + [i32] * 5 + [i64] + [vp] * 4 + [ctypes.c_size_t, vp]
             L.kgdet_coco_pack_landmarks.argtypes = [vp, i64, i32, i32, vp, vp, vp, vp]
+        if hasattr(L, 'kgdet_coco_order_dets'):
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_coco_order_dets.restype = L.kgdet_coco_scatter_dets.restype = ctypes.c_int
+            L.kgdet_coco_order_dets.argtypes = [vp, i64, i32, i32, vp, vp, i32, i32, i64, i32, i32, i32] + [vp] * 7
+            L.kgdet_coco_scatter_dets.argtypes = ([vp, i64, i32, i32, vp, i32, i64] + [vp] * 5 + [i32, i32]
+                                                  + [ctypes.POINTER(CocoPackedDets)] * 2 + [vp, vp])
         _lib = L
     return _lib
 

@@ -85,6 +85,7 @@ class RepPointsDetectorKp(nn.Module):
         """per-class numpy lists: (bboxes_in_cls, bbox_scores, kpt_in_cls), or a 1-tuple when empty"""
         if bboxes.shape[0] == 0:
             return ([np.zeros((0, 5), dtype=np.float32) for i in range(num_classes - 1)], )
+        # (no use of ``self``: runner.DeviceResults.to_host calls this without a detector)
         if torch.is_tensor(bboxes):
             bboxes, labels, kpts = bboxes.float().cpu().numpy(), labels.cpu().numpy(), kpts.float().cpu().numpy()
         return ([bboxes[labels == i, :] for i in range(num_classes - 1)], bboxes[:, 4],
@@ -97,6 +98,44 @@ class RepPointsDetectorKp(nn.Module):
         bbox_list = get(*(outs + (img_meta, self.test_cfg, rescale)))
         return [self.bbox2result_kp(det_bboxes, det_labels, det_kpts, self.bbox_head.num_classes)
                 for det_bboxes, det_labels, det_kpts in bbox_list]
+
+    def pack_detections(self, det, labels, kpts, max_per_img):
+        """(det [n, 5], labels [n], kpts [n, 3K]) device tensors -> one block [1, max_per_img, 7 + 3K] float32 in the column
+        layout of ``get_bboxes_packed_tensor`` (box, score, label, count, landmarks), with torch ops on their device; rows from
+        ``n`` on are left unwritten.  More than ``max_per_img`` detections: ``NotImplementedError`` (never cut silently)."""
+        n = int(det.shape[0])
+        if n > max_per_img:
+            raise NotImplementedError('%d detections for an image, but the device results hold max_per_img = %d rows'
+                                      % (n, max_per_img))
+        kpts = kpts.flatten(1) if kpts.dim() > 2 else kpts
+        block = torch.empty((1, max_per_img, 7 + kpts.shape[1]), dtype=torch.float32, device=det.device)
+        block[0, :, 6] = n
+        block[0, :n, :5] = det.float()
+        block[0, :n, 5] = labels.float()
+        block[0, :n, 7:] = kpts.float()
+        return block
+
+    def simple_test_batch_device(self, img, img_meta, rescale=False):
+        """``simple_test_batch`` without the download: the batch's detections as the device tensor [B, max_per_img, 7 + 3K] of
+        ``get_bboxes_packed_tensor``; where the head's packed post-processing does not apply, ``get_bboxes``'s per-image
+        tensors written into the same layout (``pack_detections``)"""
+        M = int(self.test_cfg.max_per_img)
+        if M <= 0:
+            raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
+        x = self.extract_feat(img)
+        outs = self.bbox_head(x, img_meta)
+        packed = self.bbox_head.get_bboxes_packed_tensor(*(outs + (img_meta, self.test_cfg, rescale)))
+        if packed is None:
+            bbox_list = self.bbox_head.get_bboxes(*(outs + (img_meta, self.test_cfg, rescale)))
+            packed = torch.cat([self.pack_detections(d, lab, k, M) for d, lab, k in bbox_list])
+        return packed
+
+    def aug_test_device(self, imgs, img_metas, rescale=False):
+        """``aug_test`` with the merged detections left on the device: one block [1, max_per_img, 7 + 3K]"""
+        if int(self.test_cfg.max_per_img) <= 0:
+            raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
+        det, labels, kp = self.merge_aug_detections(self.aug_candidates(imgs, img_metas), img_metas, rescale)
+        return self.pack_detections(det, labels, kp, int(self.test_cfg.max_per_img))
 
     def graphed_test_batch(self, img, img_meta, rescale=False, autocast_dtype=None, warmup=3):
         """``simple_test_batch`` for a fixed input shape and fixed image metas as ONE HIP-graph launch.
@@ -228,6 +267,7 @@ class RepPointsDetectorKp(nn.Module):
         return self.bbox2result_kp(det, labels, kp, self.bbox_head.num_classes)
 
     def forward_test(self, imgs, img_metas, **kwargs):
+        # (runner._RowSink.single repeats these checks and this dispatch for device results: keep the two in step)
         for var, name in [(imgs, 'imgs'), (img_metas, 'img_metas')]:
             if not isinstance(var, list):
                 raise TypeError('{} must be a list, but got {}'.format(name, type(var)))

@@ -16,6 +16,10 @@ similarities and four nested Python loops for the matching.  This module keeps i
 * ``pack_test_results(..., lazy_landmarks=True)``: the landmark rows stay float32 on the host and are rounded, with their
   extents, by ``kgdet_coco_pack_landmarks`` chunk by chunk (``materialize`` is the numpy route).
 
+* ``pack_device_results``: the packing of a ``runner.DeviceResults`` -- detections that never left the device -- by
+  ``kgdet_coco_order_dets`` / ``kgdet_coco_scatter_dets`` (csrc/coco_pack_dets.hip): order, exact decimal rounding, cut and
+  the landmark gather as kernels, ``kxy32`` a device tensor; ``pack_rows_restatement`` is their numpy restatement.
+
 What the device computes differently from numpy is stated in DESIGN.md: box IoU is bit-identical; for OKS the exponent
 argument is bit-identical, ``exp`` and the order of the sum over the landmarks are the device's.
 """
@@ -264,6 +268,8 @@ def materialize(packed, num_digits=None):
     coordinates.  A Packed that already holds them is returned as it is.  -> packed"""
     if getattr(packed, 'kxy32', None) is None or (packed.kxy is not None and packed.bbox is not None):
         return packed
+    if not isinstance(packed.kxy32, np.ndarray):                    # (a device tensor: pack_device_results)
+        packed.kxy32 = packed.kxy32.cpu().numpy()
     a = np.round(packed.kxy32.astype(np.float64), packed.num_digits if num_digits is None else num_digits)
     packed.bbox, packed.area, packed.kxy = _derive_from_landmarks(a)
     return packed
@@ -320,6 +326,233 @@ def pack_test_results(packed_gt, dataset, results, num_digits=4, lazy_landmarks=
         bbox, area, kxy = _landmarks_in_order(kpts, len(rows), order[0], K, num_digits)
         out['keypoints'] = _pack_dets(packed_gt, 'keypoints', img, cat, score, bbox, area, kxy, order=order)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# pack_test_results for results that stayed on the device (runner.DeviceResults; csrc/coco_pack_dets.hip)
+# ------------------------------------------------------------------------------------------------
+ROUND_LIMIT = 2.0 ** 40          # |v * 10**d| the device rounding is exact below
+
+
+def _round_half_even(values, num_digits):
+    """(rounded float64 array, number of values outside the rounding's domain -- those are returned as they are)"""
+    v = np.asarray(values, dtype=np.float64)
+    S = np.float64(10.0 ** num_digits)                              # (exact up to 10**22)
+    with np.errstate(invalid='ignore', over='ignore'):
+        a = np.abs(v)
+        p = a * S
+        bad = ~(p < ROUND_LIMIT)                                    # (a NaN is "bad" too)
+
+        def split(x):                                               # Veltkamp: x = hi + lo, 26 bits each
+            t = 134217729.0 * x
+            hi = t - (t - x)
+            return hi, x - hi
+
+        (ah, al), (sh, sl) = split(a), split(S)
+        e = ((ah * sh - p) + ah * sl + al * sh) + al * sl           # Dekker: a * S - p exactly (what fma(a, S, -p) returns)
+        f = np.floor(p)
+        r = p - f
+        up = (r > 0.5) | ((r == 0.5) & ((e > 0) | ((e == 0) & (np.fmod(f, 2.0) != 0))))
+        out = np.copysign((f + up) / S, v)
+    return np.where(bad, v, out), int(np.count_nonzero(bad))
+
+
+def round_half_even_restatement(values, num_digits):
+    """``kgdet_coco_order_dets``'s rounding in numpy: bit-equal to ``[round(float(v), num_digits) for v in values]`` for
+    ``1 <= num_digits <= 9`` and finite ``|v * 10**d| < 2**40`` (other values come back unchanged; the packing counts them and
+    raises).  With S = 10**d: p = fl(|v| * S) and the exact residual e = |v| * S - p -- an FMA on the device, a Veltkamp /
+    Dekker product here -- place the exact decimal value against the half: n = floor(p) + 1 where p - floor(p) > 1/2, or
+    == 1/2 with e > 0, or e == 0 and floor(p) odd; else floor(p).  The result is copysign(n / S, v), one correctly rounded
+    division: the double nearest to the decimal Python's ``round`` arrives at, with its sign of zero."""
+    return _round_half_even(values, num_digits)[0]
+
+
+def _pack_tables(packed_gt, dataset, N, L):
+    """(img_slot int32 [N]: sample -> index into packed_gt.img_ids, -1 unknown; cat_of_label int32 [L]: label -> index into
+    packed_gt.cat_ids, -1 unknown)"""
+    from . import _lib
+    if N != len(dataset):
+        raise ValueError('%d result blocks for a dataset of %d samples' % (N, len(dataset)))
+    if not 1 <= L <= min(len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS):
+        raise ValueError('%d labels: the dataset names %d categories, the packing kernel takes up to %d'
+                         % (L, len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS))
+    ii, ok_i = _index_of(packed_gt.img_ids, np.asarray(dataset.img_ids[:N], dtype=np.int64).reshape(-1))
+    ci, ok_c = _index_of(packed_gt.cat_ids, np.asarray(dataset.cat_ids[:L], dtype=np.int64))
+    slot = np.where(ok_i, ii, -1).astype(np.int32)
+    if len(np.unique(slot[slot >= 0])) != np.count_nonzero(slot >= 0):
+        raise ValueError('two samples share an image id: their detections share cells, which only the host packing handles')
+    return slot, np.where(ok_c, ci, -1).astype(np.int32)
+
+
+def _packed_pair(outs, start, kxy32, num_digits):
+    """the two Packed objects from per-kind dicts of arrays"""
+    b, k = outs
+    return dict(
+        bbox=Packed(kind='bbox', cell=b['cell'], start=start[0], img_idx=b['img_idx'], cat_idx=b['cat_idx'], score=b['score'],
+                    bbox=b['bbox'], area=b['area'], id=b['id'], kxy=None),
+        keypoints=Packed(kind='keypoints', cell=k['cell'], start=start[1], img_idx=k['img_idx'], cat_idx=k['cat_idx'],
+                         score=k['score'], bbox=None, area=None, id=k['id'], kxy=None, kxy32=kxy32, num_digits=num_digits))
+
+
+def pack_rows_restatement(packed_gt, dataset, rows, num_digits=4, num_labels=None):
+    """``kgdet_coco_order_dets`` + the two scans + ``kgdet_coco_scatter_dets`` in numpy on a host copy of ``rows`` float32
+    [N, M, 7 + 3K] (``runner.DeviceResults.rows``) -> {'bbox': Packed, 'keypoints': Packed}, field for field what
+    ``pack_test_results(packed_gt, dataset, dev.to_host(), num_digits, lazy_landmarks=True)`` returns.  Per image: the first
+    ``count`` rows; a row's k = its place in (label, row) order; its rank = its place among the rows of its category in
+    (descending rounded score, k) order; a row with rank < 100 / 20 goes to ``start[cell] + rank`` of the bbox / keypoints kind.
+    ``num_labels``: how many labels the detector has (None: the dataset's categories).  ``ValueError``: a value outside the
+    rounding's domain, a count outside [0, M], detections of an image the ground truth does not hold."""
+    if not isinstance(rows, np.ndarray):
+        rows = rows.cpu().numpy()
+    if not 1 <= num_digits <= 9:
+        raise ValueError('num_digits %r (1 .. 9)' % (num_digits,))
+    N, M, W = rows.shape
+    K = (W - 7) // 3
+    if W != 7 + 3 * K or K < 1:
+        raise ValueError('rows of %d floats (7 + 3K)' % W)
+    L = len(dataset.cat_ids) if num_labels is None else int(num_labels)
+    pg = packed_gt
+    slot, cat_of_label = _pack_tables(pg, dataset, N, L)
+    C = len(pg.cat_ids)
+    n_cells = len(pg.img_ids) * C
+    cuts = (MAX_DETS['bbox'], MAX_DETS['keypoints'])
+    cnt = np.zeros((2, n_cells), np.int64)
+    per_image, img_rows, n_bad = [], np.zeros(N, np.int64), 0
+    for n in range(N):
+        cf = rows[n, 0, 6]
+        if not (cf >= 0 and cf < M + 1):
+            raise ValueError('sample %d: count %r outside [0, %d]' % (n, cf, M))
+        r = rows[n, :int(cf)]
+        lf = r[:, 5]
+        with np.errstate(invalid='ignore'):
+            valid = (lf > -1) & (lf < L)
+        r = r[valid]
+        src = np.nonzero(valid)[0]
+        label = r[:, 5].astype(np.int64)
+        cat = cat_of_label[label].astype(np.int64)
+        img_rows[n] = len(r)
+        if len(r) and slot[n] < 0:
+            raise ValueError('Results do not correspond to current coco set')
+        b = r[:, :5].astype(np.float64)
+        xywhs, bad = _round_half_even(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1, b[:, 4]], axis=1),
+                                      num_digits)
+        n_bad += bad
+        k = np.empty(len(r), np.int64)
+        k[np.argsort(label, kind='mergesort')] = np.arange(len(r))
+        rank = np.full(len(r), -1, np.int64)
+        for c in np.unique(cat[cat >= 0]):
+            sel = np.nonzero(cat == c)[0]
+            rank[sel[np.lexsort((k[sel], -xywhs[sel, 4]))]] = np.arange(len(sel))
+            cnt[:, slot[n] * C + c] = np.minimum(len(sel), cuts)
+        per_image.append((src, cat, k, rank, xywhs))
+    if n_bad:
+        raise ValueError('%d box / score values are not finite or reach 2**40 / 10**%d' % (n_bad, num_digits))
+    start = np.zeros((2, n_cells + 1), np.int64)
+    np.cumsum(cnt, axis=1, out=start[:, 1:])
+    img_base = np.cumsum(img_rows) - img_rows
+    outs = []
+    for kind in range(2):
+        nk = int(start[kind, -1])
+        outs.append(dict(cell=np.full(nk, -1, np.int64), img_idx=np.full(nk, -1, np.int64), cat_idx=np.full(nk, -1, np.int64),
+                         id=np.full(nk, -1, np.int64), score=np.full(nk, np.nan), bbox=np.full((nk, 4), np.nan),
+                         area=np.full(nk, np.nan)))
+    kxy32 = np.zeros((int(start[1, -1]), 3 * K), np.float32)
+    for n, (src, cat, k, rank, xywhs) in enumerate(per_image):
+        for kind, o in enumerate(outs):
+            keep = (cat >= 0) & (rank >= 0) & (rank < cuts[kind])
+            cell = slot[n] * C + cat[keep]
+            pos = start[kind][cell] + rank[keep]
+            o['cell'][pos], o['img_idx'][pos], o['cat_idx'][pos], o['id'][pos] = cell, slot[n], cat[keep], img_base[n] + k[keep] + 1
+            o['score'][pos], o['bbox'][pos] = xywhs[keep, 4], xywhs[keep, :4]
+            o['area'][pos] = xywhs[keep, 2] * xywhs[keep, 3]
+            if kind == 1:
+                kxy32[pos] = rows[n, src[keep], 7:]
+    return _packed_pair(outs, start, kxy32, num_digits)
+
+
+def pack_device_results(packed_gt, dataset, dev_results, num_digits=4, device=None):
+    """``pack_test_results(packed_gt, dataset, dev_results.to_host(), num_digits, lazy_landmarks=True)`` without the host list:
+    ``kgdet_coco_order_dets``, two ``torch.cumsum``, ``kgdet_coco_scatter_dets`` on ``dev_results.rows`` where it lies.  The small
+    arrays of both Packed come back as numpy (``category_order``, ``accumulate`` and ``summarize`` work on them unchanged);
+    the landmark rows ``kxy32`` of the 'keypoints' Packed are a float32 tensor on the device, which ``_run_device`` slices in
+    place of an upload.  ``device``: None = where the rows are.  Rows on the CPU take ``pack_rows_restatement``.
+    ``ValueError`` as the restatement's -- ``evaluate_results`` then packs ``to_host()`` on the host."""
+    import torch
+    from . import _lib
+    rows = dev_results.rows
+    if rows is None:
+        raise ValueError('the device results were released')
+    L = int(dev_results.num_classes) - 1
+    if device is not None and str(device) != 'cpu':
+        rows = rows.to(torch.device(device))
+    if not rows.is_cuda or rows.shape[0] == 0:
+        return pack_rows_restatement(packed_gt, dataset, rows, num_digits, num_labels=L)
+    if not 1 <= num_digits <= 9:
+        raise ValueError('num_digits %r (1 .. 9)' % (num_digits,))
+    rows = rows.contiguous()
+    N, M, W = rows.shape
+    if M > _lib.COCO_ORDER_MAX_ROWS:
+        raise ValueError('%d detections per image: the packing kernel ranks up to %d' % (M, _lib.COCO_ORDER_MAX_ROWS))
+    slot, cat_of_label = _pack_tables(packed_gt, dataset, N, L)
+    C = len(packed_gt.cat_ids)
+    outs, start = _pack_rows_on_device(rows, slot, cat_of_label, C, len(packed_gt.img_ids) * C, num_digits)
+    kxy32 = outs[1].pop('kxy32')
+    host = [{f: (t.cpu().numpy() if t is not None else None) for f, t in o.items() if f != 'kxy32'} for o in outs]
+    return _packed_pair(host, start.cpu().numpy(), kxy32, num_digits)
+
+
+def _pack_rows_on_device(rows, slot, cat_of_label, C, n_cells, num_digits, alloc=None):
+    """the launches of ``pack_device_results`` on a CUDA tensor ``rows`` [N, M, W] and the two host tables ->
+    ([bbox arrays, keypoints arrays] as dicts of device tensors, start int64 [2, n_cells + 1] on the device).  ``alloc(shape,
+    dtype)``: where the kernels' outputs and intermediates come from (None: ``torch.empty`` on the rows' device)."""
+    import torch
+    from . import _lib
+    lib = _lib.lib()
+    N, M, W = rows.shape
+    L = len(cat_of_label)
+    dev = rows.device
+    if alloc is None:
+        def alloc(shape, dtype):
+            return torch.empty(shape, dtype=dtype, device=dev)
+    i32, i64, p = ctypes.c_int32, ctypes.c_int64, _lib.ptr
+    cut_b, cut_k = MAX_DETS['bbox'], MAX_DETS['keypoints']
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream()
+        slot_t, col_t = torch.from_numpy(slot).to(dev), torch.from_numpy(cat_of_label).to(dev)
+        vals, info, img_rows = alloc((N, M, 6), torch.float64), alloc((N, M, 3), torch.int32), alloc((N,), torch.int32)
+        cnt = torch.zeros((2, n_cells), dtype=torch.int32, device=dev)
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        _lib.check(lib.kgdet_coco_order_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), p(col_t), i32(L), i32(C), i64(n_cells),
+                                             i32(num_digits), i32(cut_b), i32(cut_k), p(vals), p(info), p(img_rows), p(cnt[0]),
+                                             p(cnt[1]), p(flags), stream), 'kgdet_coco_order_dets')
+        start = torch.zeros((2, n_cells + 1), dtype=torch.int64, device=dev)
+        start[:, 1:] = torch.cumsum(cnt, dim=1, dtype=torch.int64)
+        img_base = torch.cumsum(img_rows, dim=0, dtype=torch.int64) - img_rows
+        n_b, n_k, bad_value, bad_layout = torch.cat([start[:, -1], flags.to(torch.int64)]).tolist()     # (the one read-back)
+        if bad_value:
+            raise ValueError('%d box / score values are not finite or reach 2**40 / 10**%d' % (bad_value, num_digits))
+        if bad_layout:
+            raise ValueError('%d samples with a count outside [0, %d] or with detections of an image the ground truth does not '
+                             'hold' % (bad_layout, M))
+        outs, structs = [], []
+        for n, lazy in ((n_b, False), (n_k, True)):
+            o = dict(cell=alloc((n,), torch.int64), img_idx=alloc((n,), torch.int64), cat_idx=alloc((n,), torch.int64),
+                     id=alloc((n,), torch.int64), score=alloc((n,), torch.float64),
+                     bbox=None if lazy else alloc((n, 4), torch.float64), area=None if lazy else alloc((n,), torch.float64),
+                     kxy32=alloc((n, W - 7), torch.float32) if lazy else None)
+            outs.append(o)
+            structs.append(_lib.CocoPackedDets(n=n, **{f: (o[f].data_ptr() if o[f] is not None else None) for f in o}))
+        _lib.check(lib.kgdet_coco_scatter_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), i32(C), i64(n_cells), p(vals), p(info),
+                                               p(img_base), p(start[0]), p(start[1]), i32(cut_b), i32(cut_k),
+                                               ctypes.byref(structs[0]), ctypes.byref(structs[1]), p(flags), stream),
+                   'kgdet_coco_scatter_dets')
+        if int(flags[1]):
+            raise RuntimeError('kgdet_coco_scatter_dets: rows fell outside the packed arrays (counts and scans disagree)')
+        return outs, start
+
+
+def _is_device_results(results):
+    return hasattr(results, 'rows') and hasattr(results, 'to_host') and hasattr(results, 'release')
 
 
 # ------------------------------------------------------------------------------------------------
@@ -417,6 +650,8 @@ def _run_device(c, device, want_sim=True, on_device=None):
     def up(a, dtype=None):
         if a is None:
             return None
+        if torch.is_tensor(a):                                      # (rows that never left the device: pack_device_results)
+            return a.to(dev).contiguous()
         t = torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype, copy=False)))
         return t.to(dev, non_blocking=False)
 
@@ -766,13 +1001,27 @@ def evaluate_results(dataset, results, result_types=('bbox', 'keypoints'), devic
     numbers of ``coco_eval(results2json(dataset, results, ...), result_types, dataset.coco)``.  ``packed_gt``: the dataset's
     ``pack_ground_truth(dataset.coco)`` when the caller keeps it between calls (a validation hook does).  ``lazy_landmarks``
     (None = off): the landmark rows stay float32 on the host and are rounded on the device (``pack_test_results``);
-    ``device_accumulate``: ``DeviceCocoEvaluator``'s."""
+    ``device_accumulate``: ``DeviceCocoEvaluator``'s.  ``results`` may be a ``runner.DeviceResults``
+    (``single_gpu_test(..., device_results=True)``): it is packed where it lies (``pack_device_results``, always with lazy
+    landmarks) and released once packed; a ``ValueError`` of that packing sends its ``to_host()`` list down the host route."""
     for t in result_types:
         if t not in ('bbox', 'keypoints'):
             raise ValueError('unsupported result type {!r}'.format(t))
     if packed_gt is None:
         packed_gt = pack_ground_truth(dataset.coco)
-    packed = pack_test_results(packed_gt, dataset, results, lazy_landmarks=bool(lazy_landmarks))
+    packed = None
+    if _is_device_results(results):
+        try:
+            packed = pack_device_results(packed_gt, dataset, results)
+        except ValueError as e:                  # (outside the device packing's domain: the host packing of the same detections)
+            import warnings
+            warnings.warn('device results are packed on the host instead (the slow route): %s' % e, RuntimeWarning)
+            dev_results, results = results, results.to_host()
+            dev_results.release()
+        else:
+            results.release()
+    if packed is None:
+        packed = pack_test_results(packed_gt, dataset, results, lazy_landmarks=bool(lazy_landmarks))
     out = {}
     for t in result_types:
         if t not in packed:

@@ -144,14 +144,72 @@ def test_shard(n, world_size, rank):
     return idx[rank:total:world_size]
 
 
-def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False):
+class DeviceResults(object):
+    """What ``single_gpu_test(..., device_results=True)`` returns: the detections of the whole run in device memory.
+    ``rows``: ONE float32 tensor [N, M, W] -- N samples in dataset order, M = ``test_cfg.max_per_img`` rows each, W = 7 + 3K
+    columns in the layout of ``get_bboxes_packed_tensor`` (box, score, label, count, landmarks); rows at or beyond a sample's
+    count hold nothing and are never read.  ``evaluation_device.evaluate_results`` packs it where it lies
+    (``pack_device_results``).  ``to_host()``: the list the plain ``single_gpu_test`` returns, array for array (what ``--out``
+    pickles take); ``release()`` drops ``rows``.  ``num_classes``: the head's (labels are 0 .. num_classes - 2)."""
+
+    def __init__(self, rows, num_classes, unpack=None):
+        self.rows, self.num_classes, self._unpack = rows, int(num_classes), unpack
+
+    def __len__(self):
+        return 0 if self.rows is None else int(self.rows.shape[0])
+
+    def to_host(self):
+        if self.rows is None:
+            raise ValueError('the device results were released')
+        from .detector import RepPointsDetectorKp
+        unpack = self._unpack
+        if unpack is None:
+            from .heads import RepPointsHeadKp3RepCas1AssignOnce
+            unpack = RepPointsHeadKp3RepCas1AssignOnce.unpack_results
+        # (bbox2result_kp reads nothing of its detector -- it is called without one here; it has to stay that way)
+        return [RepPointsDetectorKp.bbox2result_kp(None, d.copy(), lab, k, self.num_classes)
+                for d, lab, k in unpack(self.rows.cpu().numpy())]
+
+    def release(self):
+        self.rows = None
+
+
+class _RowSink(object):
+    """where ``_test_on`` / ``_test_on_device`` leave their detections for ``device_results``: every group's packed block is
+    copied into its slice of ONE [n, M, W] tensor on the device (allocated at the first block), no download"""
+
+    def __init__(self, n):
+        self.n, self.at, self.rows = n, 0, None
+
+    def put(self, block):
+        if self.rows is None:
+            self.rows = torch.empty((self.n,) + tuple(block.shape[1:]), dtype=torch.float32, device=block.device)
+        self.rows[self.at:self.at + block.shape[0]].copy_(block)
+        self.at += block.shape[0]
+
+    def single(self, model, imgs, metas, rescale):
+        """one sample, as ``forward_test`` dispatches it: one augmentation or test-time augmentation"""
+        target = model.module if hasattr(model, 'module') else model
+        if len(imgs) != len(metas):
+            raise ValueError('num of augmentations ({}) != num of image meta ({})'.format(len(imgs), len(metas)))
+        assert imgs[0].size(0) == 1
+        if len(imgs) == 1:
+            self.put(target.simple_test_batch_device(imgs[0], metas[0], rescale=rescale))
+        else:
+            self.put(target.aug_test_device(imgs, metas, rescale=rescale))
+
+    def batch(self, model, img, metas, rescale):
+        self.put(model.simple_test_batch_device(img, metas, rescale=rescale))
+
+
+def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None):
     """results of the samples ``indices`` in that order.  imgs_per_gpu == 1: the reference's call, one image per forward
     (``model(return_loss=False, rescale=..., **data)``, tools/test.py:25-28); > 1: runs of consecutive samples with identical
     tensor shapes and one augmentation go through ``simple_test_batch`` together (the same per-image results: nothing in
     backbone / neck / head / decode / NMS mixes the images of a batch).  ``device_preprocess``: the input transform runs on the
     model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then)."""
     if device_preprocess:
-        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu)
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
@@ -171,17 +229,23 @@ def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device
                 metas = [[m] for m in data['img_meta']]
                 if to_device is not None:
                     imgs = [to_device(t) for t in imgs]
-                results.append(model(imgs, metas, return_loss=False, rescale=rescale))
+                if sink is not None:
+                    sink.single(model, imgs, metas, rescale)
+                else:
+                    results.append(model(imgs, metas, return_loss=False, rescale=rescale))
             else:
                 img = torch.stack([g['img'][0] for g in group])
                 if to_device is not None:
                     img = to_device(img)
-                results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
+                if sink is not None:
+                    sink.batch(model, img, [g['img_meta'][0] for g in group], rescale)
+                else:
+                    results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
         i += len(group)
     return results
 
 
-def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1):
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None):
     """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
     planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
     ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
@@ -205,20 +269,42 @@ def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1):
             if len(group) == 1:
                 imgs, _ = transform.separate([data['raw']] * len(data['scales']), data['scales'], data['flips'],
                                              keep_ratio=data['keep_ratio'])
-                results.append(model(imgs, [[m] for m in data['img_meta']], return_loss=False, rescale=rescale))
+                if sink is not None:
+                    sink.single(model, imgs, [[m] for m in data['img_meta']], rescale)
+                else:
+                    results.append(model(imgs, [[m] for m in data['img_meta']], return_loss=False, rescale=rescale))
             else:
                 img, _ = transform([g['raw'] for g in group], [g['scales'][0] for g in group],
                                    [g['flips'][0] for g in group], keep_ratio=data['keep_ratio'])
-                results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
+                if sink is not None:
+                    sink.batch(model, img, [g['img_meta'][0] for g in group], rescale)
+                else:
+                    results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
         i += len(group)
     return results
 
 
-def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False):
+def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False,
+                    device_results=False):
     """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
     resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
-    used then) instead of ``dataset[i]``'s host transform; same result format and order."""
-    return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess)
+    used then) instead of ``dataset[i]``'s host transform; same result format and order.  ``device_results``: the
+    detections stay on the device -- a ``DeviceResults`` comes back instead of the list (its ``to_host()`` IS that list): no
+    download and no per-class split per batch.  ``NotImplementedError`` for ``test_cfg.max_per_img <= 0`` (before the run) or
+    an image with more detections than that."""
+    if not device_results:
+        return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess)
+    target = model.module if hasattr(model, 'module') else model
+    M = int(target.test_cfg.max_per_img)
+    if M <= 0:
+        raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
+    sink = _RowSink(len(dataset))
+    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink)
+    rows = sink.rows
+    if rows is None:                            # (an empty dataset)
+        rows = torch.empty((0, M, 10), dtype=torch.float32, device=next(target.parameters()).device)
+    assert sink.at == len(dataset)
+    return DeviceResults(rows, target.bbox_head.num_classes, getattr(target.bbox_head, 'unpack_results', None))
 
 
 def collect_results(result_part, size, group=None):
@@ -419,10 +505,14 @@ class Runner(object):
     def __init__(self, model, optimizer, work_dir=None, lr_config=None, optimizer_config=None, checkpoint_config=None,
                  log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None):
         """``eval_config = dict(dataset=..., interval=1, imgs_per_gpu=1, device_preprocess=False, group=None, to_device=None,
-        result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None)``: validation after every
-        ``interval``-th epoch (``validate``); the last two are ``evaluation_device.evaluate_results``'s."""
+        result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None, device_results=False)``:
+        validation after every ``interval``-th epoch (``validate``); ``lazy_landmarks`` and ``device_accumulate`` are
+        ``evaluation_device.evaluate_results``'s, ``device_results`` is ``single_gpu_test``'s (with ``group`` it is refused:
+        ``multi_gpu_test`` gathers host lists)."""
         self.model, self.optimizer, self.work_dir = model, optimizer, work_dir
         self.eval_config = dict(eval_config) if eval_config else None
+        if self.eval_config and self.eval_config.get('device_results') and self.eval_config.get('group') is not None:
+            raise ValueError('eval_config: device_results covers single_gpu_test only, not a process group')
         self._packed_gt = None
         self.lr = LrSchedule(**(lr_config or dict(policy='step', step=[])))
         self.opt_hook = DistOptimizerHook(**(optimizer_config or {}))
@@ -536,7 +626,7 @@ class Runner(object):
             if group is not None:
                 results = multi_gpu_test(self.model, dataset, group=group, **kw)
             else:
-                results = single_gpu_test(self.model, dataset, **kw)
+                results = single_gpu_test(self.model, dataset, device_results=bool(cfg.get('device_results', False)), **kw)
         finally:
             self.model.train(was_training)
         if results is None:                     # (not rank 0)
@@ -547,7 +637,7 @@ class Runner(object):
         if device is None:
             device = next(self.model.parameters()).device
         types = [t for t in cfg.get('result_types', ('bbox', 'keypoints'))
-                 if t == 'bbox' or isinstance(results[0], tuple)]
+                 if t == 'bbox' or isinstance(results, DeviceResults) or isinstance(results[0], tuple)]
         stats = evd.evaluate_results(dataset, results, types, device=device, packed_gt=self._packed_gt,
                                      lazy_landmarks=cfg.get('lazy_landmarks'), device_accumulate=cfg.get('device_accumulate'))
         rec = OrderedDict(epoch=self.epoch)

@@ -1,7 +1,7 @@
 """Time the packed (device) evaluator against evaluation.CocoEvaluator on the same detections.
 
     python tools/time_eval.py [--images N] [--dets P] [--device cuda|cpu] [--types bbox,keypoints] [--no-host]
-                              [--lazy-landmarks] [--device-accumulate]
+                              [--lazy-landmarks] [--device-accumulate] [--device-results]
 
 A validation set of N images is built from the committed demo annotations (tests/golden/demo_dataset-32.json replicated
 under fresh image / annotation ids); every image gets P detections in the form ``single_gpu_test`` returns them (per class
@@ -13,6 +13,10 @@ be equal.  ``--no-host`` leaves the host route out (it holds every detection as 
 landmark detection).  ``--lazy-landmarks`` / ``--device-accumulate`` (a CUDA device): the device route is run a second time
 with the landmark rounding (``kgdet_coco_pack_landmarks``) and / or ``accumulate`` (``kgdet_coco_accumulate``) on the GPU and
 reported as ``device_route``; the first run, with both off, becomes ``old_route``, and the ``stats`` of the two must be equal.
+``--device-results`` (a CUDA device): the same detections are also built directly as the ``[N, M, 7 + 3K]`` device tensor a
+``single_gpu_test(..., device_results=True)`` run leaves behind and packed where they lie (``pack_device_results``:
+``kgdet_coco_order_dets`` / ``kgdet_coco_scatter_dets``), with lazy landmarks and ``--device-accumulate`` as given; reported as
+``device_results_route`` with the same phases and the peak device memory, ``stats`` equal to the other routes'.
 Prints one JSON line with seconds per stage, totals, milliseconds per image and host / device ratios."""
 import argparse
 import json
@@ -38,8 +42,9 @@ class Dataset(object):
         return len(self.img_ids)
 
 
-def build(n_images, n_dets, seed=0):
-    """(annotation dict, results): results[i] = (boxes per class, scores per class, landmarks per class), float32"""
+def build(n_images, n_dets, seed=0, rows_out=None):
+    """(annotation dict, results): results[i] = (boxes per class, scores per class, landmarks per class), float32.
+    ``rows_out(n, det, label, kpt)``: also handed every image's detections before they are split by class, in row order"""
     with open(GT) as f:
         base = json.load(f)
     rng = np.random.default_rng(seed)
@@ -89,6 +94,8 @@ def build(n_images, n_dets, seed=0):
             label[:n_jit] = np.where(keep_cat, gl[pick], label[:n_jit])
         det = np.concatenate([box[:, :2], box[:, :2] + box[:, 2:] - 1, rng.random((n_dets, 1))], axis=1).astype(np.float32)
         kpt = kpt.reshape(n_dets, 882)
+        if rows_out is not None:
+            rows_out(n, det, label, kpt)
         order = np.argsort(label, kind='mergesort')
         cut = np.searchsorted(label[order], np.arange(n_cls + 1))
         dets = [det[order[cut[c]:cut[c + 1]]] for c in range(n_cls)]
@@ -105,12 +112,24 @@ def main():
     ap.add_argument('--no-host', action='store_true')
     ap.add_argument('--lazy-landmarks', action='store_true')
     ap.add_argument('--device-accumulate', action='store_true')
+    ap.add_argument('--device-results', action='store_true')
     args = ap.parse_args()
     device = args.device or evd._default_device()
     types = args.types.split(',')
     clock = time.perf_counter
     t0 = clock()
-    gt, results = build(args.images, args.dets)
+    rows_out = rows = None
+    if args.device_results:
+        import torch
+        rows = torch.empty((args.images, args.dets, 7 + 882), dtype=torch.float32, device=device)
+        stage = torch.empty((256,) + tuple(rows.shape[1:]), dtype=torch.float32)
+
+        def rows_out(n, det, label, kpt):                         # (staged 256 images at a time: no second host copy of the set)
+            block = stage[n % 256].numpy()
+            block[:, :5], block[:, 5], block[:, 6], block[:, 7:] = det, label, len(det), kpt
+            if n % 256 == 255 or n == args.images - 1:
+                rows[n - n % 256:n + 1].copy_(stage[:n % 256 + 1])
+    gt, results = build(args.images, args.dets, rows_out=rows_out)
     index = ev.CocoIndex(gt)
     data = Dataset(index)
     out = dict(images=args.images, dets_per_image=args.dets, device=str(device), build_s=round(clock() - t0, 3))
@@ -119,12 +138,19 @@ def main():
     out['pack_ground_truth_s'] = round(clock() - t0, 4)
     evd.evaluate_packed(packed_gt, evd.pack_results(packed_gt, []), 'bbox', device)     # context, library load, first launches
 
-    def device_route(lazy, dev_acc):
-        if dev_acc:
+    def device_route(lazy, dev_acc, dev_results=None):
+        if dev_acc or dev_results is not None:
             import torch
         dev = dict()
         t0 = clock()
-        packed = evd.pack_test_results(packed_gt, data, results, lazy_landmarks=lazy)
+        if dev_results is not None:
+            on_gpu = dev_results.rows.is_cuda                                    # (CPU rows: the numpy restatement, for checks)
+            if on_gpu:
+                torch.cuda.reset_peak_memory_stats()
+            packed = evd.pack_device_results(packed_gt, data, dev_results)       # (its downloads wait for the kernels)
+            dev_results.release()
+        else:
+            packed = evd.pack_test_results(packed_gt, data, results, lazy_landmarks=lazy)
         dev['pack_s'] = clock() - t0
         got = {}
         for typ in types:
@@ -139,6 +165,8 @@ def main():
             dev[typ] = dict(kept_detections=int(len(packed[typ].score)), match_s=t1 - t0, accumulate_s=t2 - t1)
         dev['total_s'] = dev['pack_s'] + sum(dev[t]['match_s'] + dev[t]['accumulate_s'] for t in types)
         dev['ms_per_image'] = 1e3 * dev['total_s'] / args.images
+        if dev_results is not None and on_gpu:
+            dev['peak_device_gb'] = torch.cuda.max_memory_allocated() / 1e9
         return dev, got
 
     dev, got = device_route(False, False)                      # the route with packing and accumulate on the host
@@ -150,6 +178,15 @@ def main():
             assert np.array_equal(new[typ], got[typ]), (typ, new[typ], got[typ])
         out['ratio_old_new'] = out['old_route']['total_s'] / dev['total_s']
     out['device_route'] = dev
+    if args.device_results:
+        from kgdet_amd.runner import DeviceResults
+        held, rows = DeviceResults(rows, len(data.cat_ids) + 1), None          # (released once packed, as evaluate_results does)
+        dres, new = device_route(True, args.device_accumulate, held)
+        dres['device_accumulate'] = args.device_accumulate
+        for typ in types:
+            assert np.array_equal(new[typ], got[typ]), (typ, new[typ], got[typ])
+        out['device_results_route'] = dres
+        out['ratio_pack'] = dev['pack_s'] / dres['pack_s']
     if not args.no_host:
         host = dict()
         t0 = clock()
