@@ -801,6 +801,63 @@ typedef struct kgdet_preproc_job {
 } kgdet_preproc_job;
 int kgdet_image_preprocess(const kgdet_preproc_job *jobs, int32_t n_jobs, const float *norm_lut /* device [3][256] */,
                            int32_t reverse_channels, void *stream);
+/* Image preprocessing under train-time extra_aug (kgdet_amd/augment.py draws the plan; kgdet_amd/preprocess.py): the launch
+ * of kgdet_image_preprocess with photometric distortion on every source pixel and an expand / crop window in front of the
+ * resize, n_jobs <= KGDET_PREPROC_AUG_MAX_JOBS jobs, the table passed by value (capturable, no host read; mean / std are
+ * HOST pointers to 3 floats each, read during the call).  The image is float32 from the first step and is never quantised
+ * to a grey level: out = (v - mean[c]) / std[c], one subtraction and one correctly rounded division (c the OUTPUT channel,
+ * which reads source channel 2 - c when reverse_channels).  Everything is evaluated in fp32 WITHOUT contraction, every
+ * operation rounded on its own; bit-exact against kgdet_amd/preprocess.py::image_transform_restatement_aug.
+ * Colour, per source pixel (r, g, b) = the raw bytes as floats, only when KGDET_AUG_COLOUR is set (the HSV round trip then
+ * runs whatever else is on; it is not the identity in fp32), max / min taken as (b > a ? b : a) / (b < a ? b : a):
+ *   1. KGDET_AUG_BRIGHTNESS: x = x + delta        2. KGDET_AUG_CONTRAST and KGDET_AUG_CONTRAST_FIRST: x = x * alpha
+ *   3. to HSV, EPS = 2^-23: v = max(r, g, b), vmin = min(r, g, b), diff = v - vmin, s = diff / (|v| + EPS),
+ *      d = 60 / (diff + EPS); h = (g - b) * d if v == r, else (b - r) * d + 120 if v == g, else (r - g) * d + 240;
+ *      if h < 0: h += 360
+ *   4. KGDET_AUG_SATURATION: s = s * sat          5. KGDET_AUG_HUE: h = h + hue; if h > 360: h -= 360; if h < 0: h += 360
+ *   6. to RGB: s == 0 gives r = g = b = v; else h = h * (float)(6.0 / 360.0); while h < 0: h += 6; while h >= 6: h -= 6;
+ *      k = floor(h), f = h - k (k >= 6: k = 0, f = 0); t = [v, v * (1 - s), v * (1 - s * f), v * (1 - s * (1 - f))];
+ *      (b, g, r) = t[i] for the index triple of sector k in [(1,3,0), (1,0,2), (3,0,1), (0,2,1), (0,1,3), (2,1,0)]
+ *   7. KGDET_AUG_CONTRAST without KGDET_AUG_CONTRAST_FIRST: x = x * alpha
+ *   8. KGDET_AUG_PERMUTE: new[j] = old[q[j]], q[j] = (perm >> 2j) & 3 over (r, g, b)
+ * Window: the resize reads a virtual vh x vw image V; V[y][x] is the distorted raw pixel (y - oy, x - ox) where that lies
+ * inside the raw image and fill[] (raw channel order, NOT distorted) elsewhere; oy / ox may be negative (a crop), and a window
+ * that misses the raw image altogether is allowed.  The taps are those of kgdet_image_preprocess with n = vh / vw (scale_y =
+ * float32(vh) / new_h, scale_x = float32(vw) / new_w), edge-clamped at V's borders; v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 *
+ * c + lx1 * d); flip, zero padding beyond new_h x new_w and the 16-byte stores are the plain entry's.  Under
+ * KGDET_AUG_COLOUR a workgroup distorts the reachable part of an output row's two source rows once into LDS; rows whose
+ * reachable segment exceeds 1536 pixels are distorted per tap instead (the same bits either way).
+ * Errors as the plain entry (KGDET_E_UNSUPPORTED for n_jobs > KGDET_PREPROC_AUG_MAX_JOBS: the caller splits), and
+ * KGDET_E_SHAPE for vh / vw < 1, |oy| / |ox| beyond 2^20, a perm that is not a permutation of (0, 1, 2) under
+ * KGDET_AUG_PERMUTE, unknown flag bits or a stage flag without KGDET_AUG_COLOUR, and -- under KGDET_AUG_COLOUR -- a delta / alpha / sat that is not finite or beyond
+ * 65536 in magnitude or a |hue| above 720 (the bounds keep every intermediate finite and the two while loops to 3 trips). */
+#define KGDET_PREPROC_AUG_MAX_JOBS 16
+#define KGDET_AUG_COLOUR 1u
+#define KGDET_AUG_BRIGHTNESS 2u
+#define KGDET_AUG_CONTRAST 4u
+#define KGDET_AUG_CONTRAST_FIRST 8u
+#define KGDET_AUG_SATURATION 16u
+#define KGDET_AUG_HUE 32u
+#define KGDET_AUG_PERMUTE 64u
+typedef struct kgdet_preproc_aug_job {
+  const uint8_t *src;                      /* the fields of kgdet_preproc_job, with the same meaning ... */
+  int32_t src_h, src_w, src_row_bytes;
+  float *dst;
+  int64_t dst_channel_stride;
+  int32_t dst_row_stride;
+  int32_t new_h, new_w;
+  int32_t out_h, out_w;
+  float scale_y, scale_x;                  /* ... except: float32(vh) / new_h, float32(vw) / new_w */
+  int32_t flip;
+  int32_t vh, vw;                          /* the virtual image the resize reads: the crop patch, else the canvas, else the raw image */
+  int32_t oy, ox;                          /* where raw pixel (0, 0) sits in it: (top - y1, left - x1) */
+  float fill[3];                           /* V outside the raw image, in the raw image's channel order */
+  float delta, alpha, sat, hue;            /* brightness, contrast, saturation, hue (degrees); read only when their flag is set */
+  int32_t perm;                            /* q[0] | q[1] << 2 | q[2] << 4 */
+  uint32_t flags;                          /* KGDET_AUG_* */
+} kgdet_preproc_aug_job;
+int kgdet_image_preprocess_aug(const kgdet_preproc_aug_job *jobs, int32_t n_jobs, const float *mean /* host [3] */,
+                               const float *std /* host [3] */, int32_t reverse_channels, void *stream);
 /* COCO-style bbox / OKS evaluation on the device (evaluation.CocoEvaluator's similarity and matching steps;
  * kgdet_amd/evaluation_device.py packs the arrays and holds the numpy restatement).  All device pointers; one launch each
  * over the C (image, category) cells of `cells` int32 [C, 4] = (first detection, detections, first ground truth, ground

@@ -64,6 +64,18 @@ class PreprocJob(ctypes.Structure):
                 ('scale_x', ctypes.c_float), ('flip', ctypes.c_int32)]
 
 
+PREPROC_AUG_MAX_JOBS = 16   # KGDET_PREPROC_AUG_MAX_JOBS
+AUG_COLOUR, AUG_BRIGHTNESS, AUG_CONTRAST, AUG_CONTRAST_FIRST, AUG_SATURATION, AUG_HUE, AUG_PERMUTE = 1, 2, 4, 8, 16, 32, 64
+
+
+class PreprocAugJob(ctypes.Structure):
+    """kgdet_preproc_aug_job (kgdet_preproc_job + the expand / crop window and the photometric distortion of one image)"""
+    _fields_ = PreprocJob._fields_ + [
+        ('vh', ctypes.c_int32), ('vw', ctypes.c_int32), ('oy', ctypes.c_int32), ('ox', ctypes.c_int32),
+        ('fill', ctypes.c_float * 3), ('delta', ctypes.c_float), ('alpha', ctypes.c_float), ('sat', ctypes.c_float),
+        ('hue', ctypes.c_float), ('perm', ctypes.c_int32), ('flags', ctypes.c_uint32)]
+
+
 def build(force=False):
     """Compile every HIP source for gfx950 into kgdet_amd/libkgdet_hip.so (hipcc, in-tree)."""
     cmd = ['make', '-C', CSRC, '-j8']

@@ -21,6 +21,11 @@ hand the raw uint8 pixels and the planned geometry to ``kgdet_amd.preprocess.Dev
 same resize, normalisation, flip and padding for a whole batch in one HIP launch on the GPU (identical geometry and
 normalisation; its resize is defined by ``preprocess.image_transform_restatement`` and differs from the host path by one
 grey level at rounding ties).  Boxes and landmarks are transformed on the host either way.
+
+``extra_aug`` (``mmdet/datasets/extra_aug.py``: photometric distortion, expand, random crop) is served at train time:
+``kgdet_amd.augment`` makes the reference's draws and moves the ground truth -- landmarks and ignore boxes included, which the
+reference leaves behind -- and the pixels come from ``preprocess.image_transform_restatement_aug`` on the host route and from
+``kgdet_image_preprocess_aug`` on the device route (``collate_device``), the same bits for one seed.
 """
 import math
 import os
@@ -114,8 +119,8 @@ class DeepFashion2Dataset(object):
                  with_label=True, with_semantic_seg=False, with_keypoint=True, seg_prefix=None, seg_scale_factor=1,
                  extra_aug=None, resize_keep_ratio=True, corruption=None, corruption_severity=1,
                  skip_img_without_anno=True, test_mode=False, group_mode=False):
-        if with_mask or with_semantic_seg or proposal_file is not None or extra_aug is not None or corruption:
-            raise NotImplementedError('masks / proposals / extra augmentation are outside the KGDet path')
+        if with_mask or with_semantic_seg or proposal_file is not None or corruption:
+            raise NotImplementedError('masks / proposals / corruption are outside the KGDet path')
         meta = landmark_meta()
         self.gt_class_keypoints_dict = {c + 1: tuple(r) for c, r in enumerate(meta['landmark_ranges'])}
         self.flip_pairs = meta['swap_pairs']
@@ -150,6 +155,10 @@ class DeepFashion2Dataset(object):
         self.test_mode, self.group_mode = test_mode, group_mode
         self.resize_keep_ratio, self.skip_img_without_anno = resize_keep_ratio, skip_img_without_anno
         self.img_transform = ImageTransform(size_divisor=size_divisor, **img_norm_cfg)
+        self.extra_aug = None                      # (test-mode datasets ignore the keyword, as the reference does)
+        if extra_aug is not None and not test_mode:
+            from .augment import ExtraAugmentation
+            self.extra_aug = ExtraAugmentation(**extra_aug)
         if not test_mode:
             self.flag = np.array([1 if info['width'] / info['height'] > 1 else 0 for info in self.img_infos],
                                  dtype=np.uint8)
@@ -216,9 +225,15 @@ class DeepFashion2Dataset(object):
         ann = self.get_ann_info(idx)
         if len(ann['bboxes']) == 0 and self.skip_img_without_anno:
             return None
+        aug = self._draw_extra_aug(img, ann)       # (before the flip and scale draws: the reference's order)
         flip = bool(np.random.rand() < self.flip_ratio)
         scale = self._sample_scale()
-        img, img_shape, pad_shape, sf = self.img_transform(img, scale, flip, keep_ratio=self.resize_keep_ratio)
+        if aug is None:
+            img, img_shape, pad_shape, sf = self.img_transform(img, scale, flip, keep_ratio=self.resize_keep_ratio)
+        else:
+            from .preprocess import image_transform_restatement_aug
+            img, img_shape, pad_shape, sf = image_transform_restatement_aug(
+                img, aug, scale, flip, self.resize_keep_ratio, size_divisor=self.size_divisor, **self.img_norm_cfg)
         data = dict(img=torch.from_numpy(img), img_meta=self._meta(info, img_shape, pad_shape, sf, flip),
                     gt_bboxes=torch.from_numpy(bbox_transform(ann['bboxes'], img_shape, sf, flip)))
         if self.with_label:
@@ -247,22 +262,37 @@ class DeepFashion2Dataset(object):
                 metas.append(self._meta(info, img_shape, pad_shape, sf, flip))
         return dict(img=imgs, img_meta=metas)
 
-    def _plan(self, img, scale):
+    def _plan(self, img, scale, aug=None):
         from .preprocess import plan
-        return plan(img.shape[0], img.shape[1], scale, self.resize_keep_ratio, self.size_divisor)
+        h, w = img.shape[:2] if aug is None else aug.virtual_hw
+        return plan(h, w, scale, self.resize_keep_ratio, self.size_divisor)
+
+    def _draw_extra_aug(self, img, ann):
+        """``extra_aug``'s draws for this image (``None`` without the keyword) and, in place in the ``ann`` dict -- whose
+        arrays are fresh per call and are replaced, not edited -- the ground truth in the virtual image's coordinates"""
+        if self.extra_aug is None:
+            return None
+        aug = self.extra_aug.draw(img.shape[0], img.shape[1], ann['bboxes'], ann['labels'])
+        ann['bboxes'], ann['labels'], kps, ann['bboxes_ignore'] = aug.apply_gt(
+            ann['bboxes'], ann['labels'], ann.get('keypoints'), ann['bboxes_ignore'])
+        if kps is not None:
+            ann['keypoints'] = kps
+        return aug
 
     def prepare_train_raw(self, idx, img=None):
         """``prepare_train_img`` without the pixel work: ``raw`` (the decoded uint8 H x W x 3 image), the drawn ``scale`` and
         ``flip`` (the same draws from numpy's global RNG, in the same order), ``keep_ratio``, the planned ``img_meta`` and
-        the transformed ground truth -- a sample for ``collate_device``."""
+        the transformed ground truth -- a sample for ``collate_device``.  ``aug_plan``: the ``extra_aug`` draws (absent
+        without the keyword); the meta and the ground truth are then those of the plan's virtual image."""
         info = self.img_infos[idx]
         img = self.load_image(idx) if img is None else img
         ann = self.get_ann_info(idx)
         if len(ann['bboxes']) == 0 and self.skip_img_without_anno:
             return None
+        aug = self._draw_extra_aug(img, ann)
         flip = bool(np.random.rand() < self.flip_ratio)
         scale = self._sample_scale()
-        _, _, img_shape, pad_shape, sf = self._plan(img, scale)
+        _, _, img_shape, pad_shape, sf = self._plan(img, scale, aug)
         data = dict(raw=torch.from_numpy(np.ascontiguousarray(img)), scale=scale, flip=flip,
                     keep_ratio=self.resize_keep_ratio, img_meta=self._meta(info, img_shape, pad_shape, sf, flip),
                     gt_bboxes=torch.from_numpy(bbox_transform(ann['bboxes'], img_shape, sf, flip)))
@@ -279,6 +309,8 @@ class DeepFashion2Dataset(object):
                         if vis.sum() > 0:
                             inst[group, :] = inst[group, :][np.tile(vis[:, None], (1, 3))]
             data['gt_keypoints'] = torch.from_numpy(kps.astype(np.float32))
+        if aug is not None:                        # (a sample without extra_aug has the keys it always had)
+            data['aug_plan'] = aug
         return data
 
     def prepare_test_raw(self, idx, img=None):
@@ -328,15 +360,17 @@ def collate(batch):
 
 def collate_device(samples, transform):
     """``collate`` for ``prepare_train_raw`` samples: the same batch dict, with ``img`` [B, 3, H, W] made on the GPU by ONE
-    launch of ``transform`` (a ``preprocess.DeviceImageTransform``) at the batch's common size; everything else stays
-    per-image lists of host tensors.  ``Runner.train_epoch(loader, to_device=...)`` moves those as before."""
+    launch of ``transform`` (a ``preprocess.DeviceImageTransform``) at the batch's common size -- with the samples'
+    ``aug_plan``s under ``extra_aug`` --; everything else stays per-image lists of host tensors.  ``Runner.train_epoch(loader, to_device=...)`` moves those as before."""
     keep_ratio = samples[0]['keep_ratio']
     assert all(s['keep_ratio'] == keep_ratio for s in samples)
+    plans = [s.get('aug_plan') for s in samples]
+    extra = dict(aug_plans=plans) if any(p is not None for p in plans) else {}       # (without extra_aug: the call as it was)
     img, _ = transform([s['raw'] for s in samples], [s['scale'] for s in samples], [s['flip'] for s in samples],
-                       keep_ratio=keep_ratio, common_size=True)
+                       keep_ratio=keep_ratio, common_size=True, **extra)
     out = dict(img=img, img_meta=[s['img_meta'] for s in samples])
     for key in samples[0]:
-        if key not in ('raw', 'scale', 'flip', 'keep_ratio', 'img_meta'):
+        if key not in ('raw', 'scale', 'flip', 'keep_ratio', 'img_meta', 'aug_plan'):
             out[key] = [s[key] for s in samples]
     return out
 
