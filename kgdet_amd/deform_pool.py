@@ -1,6 +1,9 @@
 """Deformable PS-RoI pooling -- mirror of ``mmdet/ops/dcn/deform_pool.py``
 (DeformRoIPoolingFunction :9-69, DeformRoIPooling :75-103, DeformRoIPoolingPack :106-164,
-ModulatedDeformRoIPoolingPack :167-245) on the HIP kernels in csrc/psroi.hip (LDS-staged RoI windows, deterministic tile-gather backward).
+ModulatedDeformRoIPoolingPack :167-245) on the HIP kernels in csrc/psroi.hip: the sampling records of an (RoI, offset class) are
+built once in LDS, the map is re-laid-out cell-major so that lanes = output channels gather coalesced; grad_data comes from sorted
+per-pixel contribution lists (KGDET_PSROI_GRAD_DATA=tiles: a gather per output tile), grad_trans from one workgroup per (RoI,
+class) -- no float atomics, bit-repeatable, grad_data bit-equal to the serial float32 evaluation.
 """
 import ctypes
 
@@ -74,8 +77,9 @@ class DeformRoIPoolingFunction(Function):
             raise NotImplementedError
         data, rois, offset = ctx.saved_tensors
         grad_output = grad_output.contiguous().float()
-        # both gradients are written in full by the kernels (a gather per output tile / one workgroup per
-        # (RoI, class): no atomics, so no zero-filled accumulators -- deform_pool.py:57-59 zero-fills for atomicAdd)
+        # both gradients are written in full by the kernels (one writer per grad_data element, from its contribution list
+        # or its output tile / one workgroup per (RoI, class): no atomics, so no zero-filled accumulators --
+        # deform_pool.py:57-59 zero-fills for atomicAdd)
         grad_input = torch.empty_like(data)
         grad_rois = None
         grad_offset = torch.empty_like(offset)

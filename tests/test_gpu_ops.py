@@ -288,7 +288,7 @@ def test_deform_psroi_pooling_at_size_bit_repeatable(no_trans, S, group_size, C,
     x1 = rng.uniform(-30, 1250, R); y1 = rng.uniform(-30, 720, R)
     rois = np.stack([rng.integers(0, B, R), x1, y1, x1 + rng.uniform(8, 600, R), y1 + rng.uniform(8, 500, R)],
                     1).astype(np.float32)
-    rois[0, 1:] = [0, 0, 1343, 799]            # the whole image: its window does not fit the LDS budget (direct lane)
+    rois[0, 1:] = [0, 0, 1343, 799]            # the whole image: its samples touch every tile / pixel list of the map
     rois[1, 1:] = [40, 40, 40, 40]             # degenerate
     rois[2, 1:] = [5000, 5000, 5100, 5100]     # outside the map: count 0 everywhere
     offset = (rng.normal(size=(R, 2, P, P)) * 0.5).astype(np.float32)
