@@ -484,6 +484,26 @@ int kgdet_head_loss_forward(const kgdet_head_targets *t, const kgdet_head_loss_c
 int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
                              const float *grad_losses, const float *num_total, const kgdet_head_maps *grads,
                              const void *workspace, size_t workspace_bytes, void *stream);
+/* The same two calls with the per-image integers in DEVICE memory, so that a captured HIP graph of the training step can be
+ * replayed on batches with other ground-truth counts and other valid extents.  table: device int32 [B][4] =
+ * (num_gt, valid_h, valid_w, reserved 0) per image, 16-byte aligned, read when the kernels RUN (each workgroup reads its
+ * image's row once, as one uniform load); gt_capacity in 1..64: every gt_bboxes[b] / gt_labels[b] / gt_keypoints[b] points
+ * at a buffer of gt_capacity rows, of which the first num_gt are read -- later rows may hold anything.  The by-value num_gt /
+ * valid_h / valid_w of the descriptor are ignored.  valid_h / valid_w keep their meaning (grid units; 0 or anything beyond the
+ * grid = the whole grid).  The host cannot see the table at launch: the kernels clamp num_gt to [0, gt_capacity] and the
+ * extents to the grid, so no table content makes them read outside a buffer; range checks (1 <= num_gt <= gt_capacity, an
+ * extent of at least pos_num points) are the caller's, before it writes the table.  An image with count 0 has no positives:
+ * every valid point is a negative, and the image contributes max(0, 1) = 1 to num_total.  The selection launch is
+ * (gt_capacity, B) workgroups; workspace layout and size, arithmetic, summation orders and results are those of the by-value
+ * calls -- equal counts and extents give equal bits.  A null or misaligned table, or gt_capacity outside 1..64:
+ * KGDET_E_SHAPE, nothing written. */
+int kgdet_head_loss_forward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                                  const int32_t *table, int32_t gt_capacity, float *losses, float *num_total,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int kgdet_head_loss_backward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                                   const int32_t *table, int32_t gt_capacity, const float *grad_losses,
+                                   const float *num_total, const kgdet_head_maps *grads, const void *workspace,
+                                   size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Target assignment + the five loss families of the serial / parallel two-stage heads over the whole pyramid, without

@@ -49,6 +49,33 @@ __device__ __forceinline__ int final_assign(const float *__restrict__ dsel, int 
   return a;
 }
 
+// Ground-truth count and valid extent of image b.  TABLE = false: the by-value fields of the descriptor (checked by the host at
+// launch).  TABLE = true: row b of a device table [B][4] = (num_gt, valid_h, valid_w, 0) -- the address depends on the workgroup
+// alone, so the row is ONE 16-byte uniform (scalar) load per workgroup, not a load per point; the host cannot see its contents, so
+// the count is clamped to [0, cap] (the buffers hold cap rows) and the extent to the grid: no content reads outside a buffer.
+struct ImageRow {
+  int n_gt, vh, vw;
+};
+template <bool TABLE>
+__device__ __forceinline__ ImageRow image_row(const kgdet_head_targets &t, const int32_t *__restrict__ table, int cap, int b) {
+  int n, h, w;
+  if (TABLE) {
+    const int4 row = *reinterpret_cast<const int4 *>(table + 4 * b);
+    n = min(max(row.x, 0), cap);
+    h = row.y;
+    w = row.z;
+  } else {
+    n = t.num_gt[b];
+    h = t.valid_h[b];
+    w = t.valid_w[b];
+  }
+  ImageRow r;
+  r.n_gt = n;
+  r.vh = h > 0 ? min(h, t.H) : t.H;
+  r.vw = w > 0 ? min(w, t.W) : t.W;
+  return r;
+}
+
 }  // namespace
 
 // block (g, b), 256 threads.  dsel[b][g][i] = distance if point i is among the pos_num nearest of gt g, else +inf; row stride 64
@@ -57,12 +84,15 @@ __device__ __forceinline__ int final_assign(const float *__restrict__ dsel, int 
 // points within T = the largest distance inside a ceil(sqrt(pos_num))-sided block of grid points around the centre: that
 // block holds >= pos_num points, so every point beyond T has rank >= pos_num, and every point that precedes a candidate
 // is a candidate itself -- the all-pairs count runs over ~2 pos_num candidates instead of all H * W points.
+// TABLE: the launch is (gt_capacity, B) workgroups and the count comes from the table (image_row).
+template <bool TABLE>
 __global__ __launch_bounds__(256) void head_assign_select(const kgdet_head_targets t, int pos_num, int gmax,
-                                                          float *__restrict__ dsel) {
+                                                          float *__restrict__ dsel, const int32_t *__restrict__ table, int cap) {
   extern __shared__ float dist[];                    // [N] distances, then [N] candidate indices
   __shared__ int s_tbits, s_count;
   const int g = blockIdx.x, b = blockIdx.y, N = t.H * t.W, tid = threadIdx.x;
-  if (g >= t.num_gt[b]) return;
+  const ImageRow im = image_row<TABLE>(t, table, cap, b);
+  if (g >= im.n_gt) return;
   int *cand = reinterpret_cast<int *>(dist + N);
   const float *box = t.gt_bboxes[b] + 4 * g;
   // point_assigner.py:69-71: centre and size of the gt; :93-95: ((p - centre) / size).norm(dim=1)
@@ -70,7 +100,7 @@ __global__ __launch_bounds__(256) void head_assign_select(const kgdet_head_targe
   const float w = fmaxf(box[2] - box[0], 1e-6f), h = fmaxf(box[3] - box[1], 1e-6f);
   if (tid == 0) { s_tbits = 0; s_count = 0; }
   // the image's valid extent (point_target_kp.py:107-118: the assigner only sees the points inside it)
-  const int vh = t.valid_h[b] > 0 ? min(t.valid_h[b], t.H) : t.H, vw = t.valid_w[b] > 0 ? min(t.valid_w[b], t.W) : t.W;
+  const int vh = im.vh, vw = im.vw;
   for (int i = tid; i < N; i += 256) {
     const int col = i % t.W, row = i / t.W;
     const float px = (float)col * t.stride, py = (float)row * t.stride;
@@ -134,19 +164,21 @@ struct PointCtx {
 }  // namespace
 
 // block (tile of 64 points, channel group, image); 256 threads = 4 waves, lane = point, waves take rows round-robin.
-template <bool BACKWARD>
+template <bool BACKWARD, bool TABLE>
 __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t, const kgdet_head_loss_cfg cfg,
                                                       const kgdet_head_maps maps, const float *__restrict__ dsel, int gmax,
                                                       int rows_per_group, float *__restrict__ partial,
                                                       const float *__restrict__ num_total_dev,
-                                                      const float *__restrict__ upstream, kgdet_head_maps grads) {
+                                                      const float *__restrict__ upstream, kgdet_head_maps grads,
+                                                      const int32_t *__restrict__ table, int cap) {
   __shared__ int s_nvis[kMaxGt];
   __shared__ float s_part[4][9];
   const int N = t.H * t.W, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = blockIdx.x * 64 + lane;
   const bool live = i < N;
   const int ic = min(i, N - 1);
-  const int n_gt = t.num_gt[b];
+  const ImageRow im = image_row<TABLE>(t, table, cap, b);
+  const int n_gt = im.n_gt;
   const int K = t.num_keypoints, K2 = 2 * K, C = t.num_classes;
   // visible keypoints per gt (kpt_weights.sum(1) / 2 of KP3:641-644)
   for (int g = wave; g < n_gt; g += 4) {
@@ -164,7 +196,7 @@ __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t
   p.py = (float)(ic / t.W) * t.stride;
   const float *gbox = t.gt_bboxes[b] + 4 * max(p.a - 1, 0);
   const float *gkp = t.gt_keypoints[b] + (long long)max(p.a - 1, 0) * K * 3;
-  const int vh = t.valid_h[b] > 0 ? min(t.valid_h[b], t.H) : t.H, vw = t.valid_w[b] > 0 ? min(t.valid_w[b], t.W) : t.W;
+  const int vh = im.vh, vw = im.vw;
   const bool inside = ic / t.W < vh && ic % t.W < vw;                // (a point outside is never assigned: p.a == 0)
   const float label_w = p.a > 0 ? cfg.pos_weight : (inside ? 1.0f : 0.0f);   // point_target_kp.py:140-147, unmap fill 0
   const float kp_w = p.nvis > 0 ? 1.0f / (float)(2 * p.nvis) * 4.0f : 0.0f;
@@ -240,10 +272,13 @@ __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t
 }
 
 // one block: n_pos per image -> num_total; partials in fixed order; the nine losses
+// (an image whose count is 0 -- the table route only -- has no positives and adds max(0, 1) = 1)
+template <bool TABLE>
 __global__ __launch_bounds__(256) void head_loss_finish(const kgdet_head_targets t, const kgdet_head_loss_cfg cfg,
                                                         const float *__restrict__ dsel, int gmax,
                                                         const float *__restrict__ partial, int num_partials,
-                                                        float *__restrict__ losses, float *__restrict__ num_total_out) {
+                                                        float *__restrict__ losses, float *__restrict__ num_total_out,
+                                                        const int32_t *__restrict__ table, int cap) {
   __shared__ float red[4][9];
   __shared__ int s_pos[4];
   __shared__ float s_total;
@@ -251,7 +286,8 @@ __global__ __launch_bounds__(256) void head_loss_finish(const kgdet_head_targets
   float total = 0.f;
   for (int b = 0; b < t.B; ++b) {
     int cnt = 0;
-    for (int i = tid; i < N; i += 256) cnt += final_assign(dsel, b, gmax, t.num_gt[b], N, i) > 0 ? 1 : 0;
+    const int n_gt = image_row<TABLE>(t, table, cap, b).n_gt;
+    for (int i = tid; i < N; i += 256) cnt += final_assign(dsel, b, gmax, n_gt, N, i) > 0 ? 1 : 0;
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
     __syncthreads();
     if (lane == 0) s_pos[wave] = cnt;
@@ -284,13 +320,14 @@ using namespace kgdet;
 
 extern "C" {
 
-static int head_check(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, int *gmax) {
+// by_table: the counts and extents live in device memory (the *_table entry points): the by-value fields are not looked at
+static int head_check(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, int *gmax, bool by_table = false) {
   KGDET_CHECK_SHAPE(t && cfg, "null descriptor");
   KGDET_CHECK_SHAPE(t->B >= 1 && t->B <= kMaxImages, "1..%d images per call", kMaxImages);
   KGDET_CHECK_SHAPE(t->H > 0 && t->W > 0 && t->H * t->W <= kMaxPoints, "point grid beyond %d points", kMaxPoints);
   KGDET_CHECK_SHAPE(t->num_classes > 0 && t->num_keypoints > 0, "bad channel counts");
   KGDET_CHECK_SHAPE(cfg->pos_num >= 1 && cfg->normalize_term > 0.0f, "bad assigner / normaliser");
-  for (int b = 0; b < t->B; ++b) {
+  for (int b = 0; b < t->B && !by_table; ++b) {
     const int vh = t->valid_h[b] > 0 ? (t->valid_h[b] < t->H ? t->valid_h[b] : t->H) : t->H;
     const int vw = t->valid_w[b] > 0 ? (t->valid_w[b] < t->W ? t->valid_w[b] : t->W) : t->W;
     KGDET_CHECK_SHAPE(t->valid_h[b] >= 0 && t->valid_w[b] >= 0 && (long long)vh * vw >= cfg->pos_num,
@@ -298,13 +335,22 @@ static int head_check(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cf
   }
   int g = 0;
   for (int b = 0; b < t->B; ++b) {
-    KGDET_CHECK_SHAPE(t->num_gt[b] >= 1 && t->num_gt[b] <= kMaxGt, "image %d: %d ground-truth boxes (1..%d)", b,
-                      t->num_gt[b], kMaxGt);
+    if (!by_table) {
+      KGDET_CHECK_SHAPE(t->num_gt[b] >= 1 && t->num_gt[b] <= kMaxGt, "image %d: %d ground-truth boxes (1..%d)", b,
+                        t->num_gt[b], kMaxGt);
+      if (t->num_gt[b] > g) g = t->num_gt[b];
+    }
     KGDET_CHECK_SHAPE(t->gt_bboxes[b] && t->gt_keypoints[b], "null ground-truth pointer");
-    if (t->num_gt[b] > g) g = t->num_gt[b];
   }
   for (int k = 0; k < 6; ++k) KGDET_CHECK_SHAPE(cfg->beta[k] > 0.0f, "beta must be positive");
   *gmax = g;
+  return KGDET_OK;
+}
+
+static int head_table_check(const int32_t *table, int32_t gt_capacity) {
+  KGDET_CHECK_SHAPE(table != nullptr, "null target table");
+  KGDET_CHECK_SHAPE(reinterpret_cast<uintptr_t>(table) % 16 == 0, "the target table must be 16-byte aligned");
+  KGDET_CHECK_SHAPE(gt_capacity >= 1 && gt_capacity <= kMaxGt, "gt_capacity %d (1..%d)", gt_capacity, kMaxGt);
   return KGDET_OK;
 }
 
@@ -329,10 +375,13 @@ size_t kgdet_head_loss_workspace_bytes(const kgdet_head_targets *t) {
          256;
 }
 
-int kgdet_head_loss_forward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
-                            float *losses, float *num_total, void *workspace, size_t workspace_bytes, void *stream) {
+// both routes: `table` == nullptr is the by-value route (select grid = the largest count), else (gt_capacity, B) workgroups
+static int head_forward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                        const int32_t *table, int32_t cap, float *losses, float *num_total, void *workspace,
+                        size_t workspace_bytes, void *stream) {
   int gmax = 0;
-  if (int rc = head_check(t, cfg, &gmax)) return rc;
+  if (int rc = head_check(t, cfg, &gmax, table != nullptr)) return rc;
+  if (table) gmax = cap;
   KGDET_CHECK_SHAPE(maps && losses && num_total, "null pointer");
   for (int s = 0; s < 3; ++s) KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s], "null prediction map");
   const size_t need = kgdet_head_loss_workspace_bytes(t);
@@ -345,27 +394,27 @@ int kgdet_head_loss_forward(const kgdet_head_targets *t, const kgdet_head_loss_c
   float *dsel = reinterpret_cast<float *>(workspace);
   float *partial = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) +
                                              align_up((size_t)t->B * kMaxGt * N * sizeof(float), 256));
-  hipLaunchKernelGGL(head_assign_select, dim3(gmax, t->B), dim3(256), (size_t)N * 2 * sizeof(float), (hipStream_t)stream, *t,
-                     cfg->pos_num, kMaxGt, dsel);
+  hipLaunchKernelGGL(table ? head_assign_select<true> : head_assign_select<false>, dim3(gmax, t->B), dim3(256),
+                     (size_t)N * 2 * sizeof(float), (hipStream_t)stream, *t, cfg->pos_num, kMaxGt, dsel, table, (int)cap);
   KGDET_CHECK_LAUNCH("head_assign_select");
   int groups = 0;
   const int rows = head_rows_per_group(t, &groups);
   const int tiles = ceil_div(N, 64);
   kgdet_head_maps none = {};
-  hipLaunchKernelGGL(head_loss_rows<false>, dim3(tiles, groups, t->B), dim3(256), 0, (hipStream_t)stream, *t, *cfg, *maps,
-                     dsel, kMaxGt, rows, partial, (const float *)nullptr, (const float *)nullptr, none);
+  hipLaunchKernelGGL((table ? head_loss_rows<false, true> : head_loss_rows<false, false>), dim3(tiles, groups, t->B), dim3(256), 0, (hipStream_t)stream, *t, *cfg,
+                     *maps, dsel, kMaxGt, rows, partial, (const float *)nullptr, (const float *)nullptr, none, table, (int)cap);
   KGDET_CHECK_LAUNCH("head_loss_rows<forward>");
-  hipLaunchKernelGGL(head_loss_finish, dim3(1), dim3(256), 0, (hipStream_t)stream, *t, *cfg, dsel, kMaxGt, partial,
-                     tiles * groups * t->B, losses, num_total);
+  hipLaunchKernelGGL(table ? head_loss_finish<true> : head_loss_finish<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *t, *cfg, dsel, kMaxGt, partial,
+                     tiles * groups * t->B, losses, num_total, table, (int)cap);
   KGDET_CHECK_LAUNCH("head_loss_finish");
   return KGDET_OK;
 }
 
-int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
-                             const float *grad_losses, const float *num_total, const kgdet_head_maps *grads,
-                             const void *workspace, size_t workspace_bytes, void *stream) {
+static int head_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                         const int32_t *table, int32_t cap, const float *grad_losses, const float *num_total,
+                         const kgdet_head_maps *grads, const void *workspace, size_t workspace_bytes, void *stream) {
   int gmax = 0;
-  if (int rc = head_check(t, cfg, &gmax)) return rc;
+  if (int rc = head_check(t, cfg, &gmax, table != nullptr)) return rc;
   KGDET_CHECK_SHAPE(maps && grads && grad_losses && num_total, "null pointer");
   for (int s = 0; s < 3; ++s)
     KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s] && grads->cls[s] && grads->bbox[s] && grads->kpt[s],
@@ -379,10 +428,35 @@ int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_
   const float *dsel = reinterpret_cast<const float *>(workspace);
   int groups = 0;
   const int rows = head_rows_per_group(t, &groups);
-  hipLaunchKernelGGL(head_loss_rows<true>, dim3(ceil_div(N, 64), groups, t->B), dim3(256), 0, (hipStream_t)stream, *t, *cfg,
-                     *maps, dsel, kMaxGt, rows, (float *)nullptr, num_total, grad_losses, *grads);
+  hipLaunchKernelGGL((table ? head_loss_rows<true, true> : head_loss_rows<true, false>), dim3(ceil_div(N, 64), groups, t->B), dim3(256), 0, (hipStream_t)stream, *t,
+                     *cfg, *maps, dsel, kMaxGt, rows, (float *)nullptr, num_total, grad_losses, *grads, table, (int)cap);
   KGDET_CHECK_LAUNCH("head_loss_rows<backward>");
   return KGDET_OK;
+}
+
+int kgdet_head_loss_forward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                            float *losses, float *num_total, void *workspace, size_t workspace_bytes, void *stream) {
+  return head_forward(t, cfg, maps, nullptr, 0, losses, num_total, workspace, workspace_bytes, stream);
+}
+
+int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                             const float *grad_losses, const float *num_total, const kgdet_head_maps *grads,
+                             const void *workspace, size_t workspace_bytes, void *stream) {
+  return head_backward(t, cfg, maps, nullptr, 0, grad_losses, num_total, grads, workspace, workspace_bytes, stream);
+}
+
+int kgdet_head_loss_forward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                                  const int32_t *table, int32_t gt_capacity, float *losses, float *num_total, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  if (int rc = head_table_check(table, gt_capacity)) return rc;
+  return head_forward(t, cfg, maps, table, gt_capacity, losses, num_total, workspace, workspace_bytes, stream);
+}
+
+int kgdet_head_loss_backward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+                                   const int32_t *table, int32_t gt_capacity, const float *grad_losses, const float *num_total,
+                                   const kgdet_head_maps *grads, const void *workspace, size_t workspace_bytes, void *stream) {
+  if (int rc = head_table_check(table, gt_capacity)) return rc;
+  return head_backward(t, cfg, maps, table, gt_capacity, grad_losses, num_total, grads, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

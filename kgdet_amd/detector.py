@@ -73,13 +73,20 @@ class RepPointsDetectorKp(nn.Module):
         conv1x1.invalidate_inference_caches()
         return super(RepPointsDetectorKp, self).train(mode)
 
-    def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore=None):
+    def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore=None, gt_table=None):
+        """``gt_table``: the device table of a ``static_batch.StaticBatch`` (ground-truth counts and valid extents in device
+        memory, ground truth in buffers of fixed capacity); the KGDet head only -- any other head raises
+        ``NotImplementedError``"""
         from . import conv1x1
+        if gt_table is not None and not getattr(self.bbox_head, 'takes_gt_table', False):
+            raise NotImplementedError('%s takes no ground-truth table (the KGDet head does)' % type(self.bbox_head).__name__)
         with conv1x1.step_scope():    # the split-bf16 convolutions' weight images: one pack launch per step
             x = self.extract_feat(img)
             outs = self.bbox_head(x, img_metas)
         loss_inputs = outs + (gt_bboxes, gt_labels, gt_keypoints, img_metas, self.train_cfg)
-        return self.bbox_head.loss(*loss_inputs, gt_bboxes_ignore=gt_bboxes_ignore)
+        if gt_table is None:
+            return self.bbox_head.loss(*loss_inputs, gt_bboxes_ignore=gt_bboxes_ignore)
+        return self.bbox_head.loss(*loss_inputs, gt_bboxes_ignore=gt_bboxes_ignore, gt_table=gt_table)
 
     def bbox2result_kp(self, bboxes, labels, kpts, num_classes):
         """per-class numpy lists: (bboxes_in_cls, bbox_scores, kpt_in_cls), or a 1-tuple when empty"""

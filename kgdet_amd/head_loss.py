@@ -9,6 +9,11 @@ module computes the same nine numbers and the same nine gradients from the raw p
 tables, without materialising a target or weight tensor and without a host read.
 
 ``KGDET_FUSED_HEAD_LOSS=0`` selects the torch chain (A/B, and what the parity tests compare against).
+
+The table route (``gt_table`` / ``gt_capacity``): the per-image ground-truth counts and valid extents are read from a device
+table [B, 4] int32 = (num_gt, valid_h, valid_w, 0) when the kernels run, and every ground-truth tensor is a buffer of
+``gt_capacity`` rows of which the first ``num_gt`` count -- the launch arguments no longer depend on the batch
+(``static_batch.StaticBatch`` holds such buffers).  The padded rows exist for the kernels alone: with a table there is no torch chain to fall to, ``why_not`` names what stands in the way.
 """
 import ctypes
 import os
@@ -47,52 +52,83 @@ def _maps(tensors):
 
 
 def applicable(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore,
-               all_valid=True, valid_sizes=None):
+               all_valid=True, valid_sizes=None, gt_table=None, gt_capacity=None):
     """the fused kernels cover exactly the case ``points.dense_targets_applicable`` covers for one level, on the GPU, in
-    float32; ``valid_sizes``: per image the (rows, columns) of the grid inside its pad_shape (None: all of it)"""
+    float32; ``valid_sizes``: per image the (rows, columns) of the grid inside its pad_shape (None: all of it).
+    ``gt_table`` (a device table of counts and extents, see the module's docstring): the ground-truth tensors are buffers of
+    ``gt_capacity`` rows -- the per-image count checks become checks of the capacity, the extents are the table's."""
+    return why_not(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore,
+                   all_valid, valid_sizes, gt_table, gt_capacity) is None
+
+
+def table_capacity(gt_bboxes, gt_capacity=None):
+    """the row capacity of the table route's ground-truth buffers: ``gt_capacity``, or the buffers' own length"""
+    return int(gt_bboxes[0].shape[0]) if gt_capacity is None else int(gt_capacity)
+
+
+def why_not(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore,
+            all_valid=True, valid_sizes=None, gt_table=None, gt_capacity=None):
+    """None when ``applicable``, else the reason in words"""
     from .losses import FocalLoss, SmoothL1Loss
     from .points import dense_targets_applicable
-    if not ENABLED or head.sampling or not head.use_sigmoid_cls or len(head.point_strides) != 1:
-        return False
+    if not ENABLED:
+        return 'the fused head loss is switched off (KGDET_FUSED_HEAD_LOSS=0)'
+    if head.sampling or not head.use_sigmoid_cls or len(head.point_strides) != 1:
+        return 'the head samples, has a softmax classifier or more than one pyramid level'
     if not dense_targets_applicable(cfg, 1, all_valid, gt_bboxes_ignore):
-        return False
+        return 'the assigner is no PointAssigner with a fixed pos_num, or the batch carries gt_bboxes_ignore'
     for stage in (1, 2, 3):
         lc, lb, lk = (getattr(head, 'loss_%s_%d' % (n, stage)) for n in ('cls', 'bbox', 'kpt'))
         if type(lc) is not FocalLoss or lc.reduction != 'mean' or type(lb) is not SmoothL1Loss or \
                 type(lk) is not SmoothL1Loss or lb.reduction != 'mean' or lk.reduction != 'mean':
-            return False
+            return 'stage %d: the losses are not FocalLoss / SmoothL1Loss with reduction "mean"' % stage
     t0 = cls_scores[0][0]
     B, _, H, W = t0.shape
     if not t0.is_cuda or B > MAX_IMAGES or H * W > MAX_POINTS or torch.is_autocast_enabled():
-        return False
+        return 'maps off the GPU, more than %d images, more than %d points, or autocast' % (MAX_IMAGES, MAX_POINTS)
     for group in (cls_scores, kpt_preds, bbox_preds):
         for per_level in group:
             if len(per_level) != 1 or per_level[0].dtype != torch.float32:
-                return False
+                return 'more than one level, or maps that are not float32'
     if cfg.assigner.get('pos_num', 3) > H * W:
-        return False
+        return 'pos_num beyond the number of points'
     if valid_sizes is not None and any(vh * vw < cfg.assigner.get('pos_num', 3) for vh, vw in valid_sizes):
-        return False
+        return 'an image with fewer valid points than pos_num'
+    cap = None
+    if gt_table is not None:
+        cap = table_capacity(gt_bboxes, gt_capacity)
+        if not 1 <= cap <= MAX_GT:
+            return 'gt_capacity %d outside 1..%d' % (cap, MAX_GT)
+        if gt_table.dtype != torch.int32 or tuple(gt_table.shape) != (B, 4) or gt_table.device != t0.device or \
+                not gt_table.is_contiguous():
+            return 'the table is not a contiguous int32 [%d, 4] tensor on the maps\' device' % B
+        if gt_labels is None or any(l is None for l in gt_labels):
+            return 'the table route needs label buffers'
     for b in range(B):
         g = gt_bboxes[b].shape[0]
-        if g < 1 or g > MAX_GT or gt_bboxes[b].dtype != torch.float32 or gt_keypoints[b].dtype != torch.float32 or \
+        if cap is not None:
+            if g < cap or gt_keypoints[b].shape[0] < cap or gt_labels[b].shape[0] < cap:
+                return 'image %d: a ground-truth buffer is shorter than the capacity of %d rows' % (b, cap)
+        elif g < 1 or g > MAX_GT:
+            return 'image %d: %d ground truths (1..%d)' % (b, g, MAX_GT)
+        if gt_bboxes[b].dtype != torch.float32 or gt_keypoints[b].dtype != torch.float32 or \
                 gt_keypoints[b].shape[1:] != (head.num_keypts, 3):
-            return False
+            return 'image %d: ground truth that is not float32 [n, 4] and [n, %d, 3]' % (b, head.num_keypts)
         # the kernels dereference the raw ground-truth pointers: they must live on the maps' device (CPU-resident or
         # other-GPU ground truth takes the torch chain, which raises torch's own device-mismatch error or works)
         if gt_bboxes[b].device != t0.device or gt_keypoints[b].device != t0.device:
-            return False
+            return 'image %d: ground truth on another device than the maps' % b
         if gt_labels is not None and gt_labels[b] is not None and (gt_labels[b].dtype != torch.int64 or
                                                                    gt_labels[b].device != t0.device):
-            return False
-    return True
+            return 'image %d: labels that are not int64 on the maps\' device' % b
+    return None
 
 
 class _HeadLoss(torch.autograd.Function):
     """(cls_1..3, bbox_1..3, kpt_1..3 prediction maps) -> nine 0-dim losses"""
 
     @staticmethod
-    def forward(ctx, targets, cfg, keep, *maps):
+    def forward(ctx, targets, cfg, keep, table, cap, *maps):
         L = _lib.lib()
         maps = tuple(m.contiguous() for m in maps)
         dev = maps[0].device
@@ -100,10 +136,17 @@ class _HeadLoss(torch.autograd.Function):
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         out = torch.empty(10, dtype=torch.float32, device=dev)          # nine losses + num_total
         hm = _maps(maps)
-        _lib.check(L.kgdet_head_loss_forward(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm), _lib.ptr(out),
-                                             ctypes.c_void_p(out.data_ptr() + 36), _lib.ptr(ws), ctypes.c_size_t(ws_bytes),
-                                             _lib.current_stream()), 'kgdet_head_loss_forward')
+        tail = (_lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 36), _lib.ptr(ws), ctypes.c_size_t(ws_bytes),
+                _lib.current_stream())
+        if table is None:
+            _lib.check(L.kgdet_head_loss_forward(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm), *tail),
+                       'kgdet_head_loss_forward')
+        else:
+            _lib.check(L.kgdet_head_loss_forward_table(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm),
+                                                       _lib.ptr(table), ctypes.c_int32(cap), *tail),
+                       'kgdet_head_loss_forward_table')
         ctx.targets, ctx.cfg, ctx.keep, ctx.ws, ctx.ws_bytes, ctx.out = targets, cfg, keep, ws, ws_bytes, out
+        ctx.table, ctx.cap = table, cap
         ctx.save_for_backward(*maps)
         return tuple(out[k] for k in range(9))
 
@@ -123,16 +166,24 @@ class _HeadLoss(torch.autograd.Function):
         up = torch.stack(gl)
         grads = tuple(torch.empty_like(m) for m in maps)
         hm, hg = _maps(maps), _maps(grads)
-        _lib.check(_lib.lib().kgdet_head_loss_backward(
-            ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), _lib.ptr(up),
-            ctypes.c_void_p(ctx.out.data_ptr() + 36), ctypes.byref(hg), _lib.ptr(ctx.ws), ctypes.c_size_t(ctx.ws_bytes),
-            _lib.current_stream()), 'kgdet_head_loss_backward')
-        return (None, None, None) + grads
+        tail = (_lib.ptr(up), ctypes.c_void_p(ctx.out.data_ptr() + 36), ctypes.byref(hg), _lib.ptr(ctx.ws),
+                ctypes.c_size_t(ctx.ws_bytes), _lib.current_stream())
+        if ctx.table is None:
+            _lib.check(_lib.lib().kgdet_head_loss_backward(
+                ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), *tail), 'kgdet_head_loss_backward')
+        else:
+            _lib.check(_lib.lib().kgdet_head_loss_backward_table(
+                ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), _lib.ptr(ctx.table),
+                ctypes.c_int32(ctx.cap), *tail), 'kgdet_head_loss_backward_table')
+        return (None, None, None, None, None) + grads
 
 
-def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, valid_sizes=None):
+def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, valid_sizes=None,
+              gt_table=None, gt_capacity=None):
     """The nine losses of ``head.loss`` as a dict of 0-dim tensors (one list entry per level, as the reference returns).
-    ``cls_scores`` / ``kpt_preds`` / ``bbox_preds``: three stages x [one level] of NCHW maps."""
+    ``cls_scores`` / ``kpt_preds`` / ``bbox_preds``: three stages x [one level] of NCHW maps.  ``gt_table``: the table route
+    (the module's docstring) -- counts and extents are the table's, ``valid_sizes`` is not used."""
+    cap = None if gt_table is None else table_capacity(gt_bboxes, gt_capacity)
     t0 = cls_scores[0][0]
     B, C, H, W = t0.shape
     t = HeadTargets()
@@ -145,8 +196,9 @@ def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels
             raise ValueError('No gt or bboxes')
         lab = None if gt_labels is None or gt_labels[b] is None else gt_labels[b].contiguous()
         keep += [bb, kp, lab]
-        t.num_gt[b] = bb.shape[0]
-        if valid_sizes is not None:
+        if gt_table is None:
+            t.num_gt[b] = bb.shape[0]
+        if valid_sizes is not None and gt_table is None:
             t.valid_h[b], t.valid_w[b] = int(valid_sizes[b][0]), int(valid_sizes[b][1])
         t.gt_bboxes[b], t.gt_keypoints[b] = bb.data_ptr(), kp.data_ptr()
         t.gt_labels[b] = lab.data_ptr() if lab is not None else None
@@ -162,7 +214,7 @@ def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels
         c.loss_weight[s], c.loss_weight[3 + s], c.loss_weight[6 + s] = float(lc.loss_weight), float(lb.loss_weight), \
             float(lk.loss_weight)
     maps = [cls_scores[s][0] for s in range(3)] + [bbox_preds[s][0] for s in range(3)] + [kpt_preds[s][0] for s in range(3)]
-    out = _HeadLoss.apply(t, c, keep, *maps)
+    out = _HeadLoss.apply(t, c, keep, gt_table, cap, *maps)
     names = ['loss_cls_1', 'loss_cls_2', 'loss_cls_3', 'loss_bbox_1', 'loss_bbox_2', 'loss_bbox_3',
              'loss_kpt_1', 'loss_kpt_2', 'loss_kpt_3']
     return {n: [v] for n, v in zip(names, out)}

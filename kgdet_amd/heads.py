@@ -299,6 +299,8 @@ class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
     """Three-stage keypoint-guided RepPoints head (stage 1 plain, stages 2-3 deformable), one target
     assignment shared by all stages."""
 
+    takes_gt_table = True      # `loss(..., gt_table=)`: counts and extents from device memory (head_loss's table route)
+
     def __init__(self,
                  num_classes,
                  in_channels,
@@ -457,7 +459,11 @@ class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
 
     def loss(self, cls_scores_1, cls_scores_2, cls_scores_3, keypts_preds_1, keypts_preds_2, keypts_preds_3,
              bbox_preds_1, bbox_preds_2, bbox_preds_3, gt_bboxes, gt_labels, gt_keypoints, img_metas, cfg,
-             gt_bboxes_ignore=None):
+             gt_bboxes_ignore=None, gt_table=None):
+        """``gt_table``: device int32 [B, 4] = (num_gt, valid_h, valid_w, 0) per image (``static_batch.StaticBatch``) -- the
+        ground-truth tensors are then buffers of equal capacity whose first ``num_gt`` rows count, the valid extents are the
+        table's and not ``img_metas``', and the fused kernels are the only route: the padded rows never reach the torch chain
+        (``NotImplementedError`` naming the reason where the kernels do not apply)."""
         featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores_3]
         assert len(featmap_sizes) == len(self.point_generators)
         label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
@@ -465,6 +471,16 @@ class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
 
         if cfg.uniform.assigner['type'] != 'PointAssigner':
             raise NotImplementedError
+        if gt_table is not None:
+            from . import head_loss
+            stages = ((cls_scores_1, cls_scores_2, cls_scores_3), (keypts_preds_1, keypts_preds_2, keypts_preds_3),
+                      (bbox_preds_1, bbox_preds_2, bbox_preds_3))
+            reason = head_loss.why_not(self, cfg.uniform, stages[0], stages[1], stages[2], gt_bboxes, gt_labels, gt_keypoints,
+                                       gt_bboxes_ignore, gt_table=gt_table)
+            if reason is not None:
+                raise NotImplementedError('a ground-truth table needs the fused head-loss kernels: ' + reason)
+            return head_loss.head_loss(self, cfg.uniform, stages[0], stages[1], stages[2], gt_bboxes, gt_labels,
+                                       gt_keypoints, gt_table=gt_table)
         # the part of every level's grid inside each image's own pad_shape (KP3:524-535; host arithmetic on the image
         # metas): a batch of mixed shapes leaves some grid points invalid in almost every step, and they take the SAME
         # sync-free path (round 6: valid extents in the dense targets and in the fused loss)
