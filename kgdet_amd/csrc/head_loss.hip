@@ -24,6 +24,8 @@
 //   head_loss_backward   same rows: grad of every prediction map, written in full (zeros where the reference's weight is 0).
 //
 // No tensor of targets or weights exists; nothing is read by the host.  Deterministic (fixed summation orders).
+// The loss rows' arithmetic, the PointAssigner frame of a gt, the reductions and the host-side skeleton are loss_math.h's, shared
+// with serial_loss.hip; the rank-based selection, the row enumeration, the decode order and the keypoint weight are this file's.
 #include <float.h>
 
 #include "common.h"
@@ -33,8 +35,6 @@ namespace kgdet {
 
 namespace {
 
-constexpr int kMaxImages = KGDET_HEAD_MAX_IMAGES;
-constexpr int kMaxGt = 64;
 constexpr int kMaxPoints = 4096;
 
 // the assignment of point i of image b from the per-gt selections: point_assigner.py:106-117 (`min_dist <
@@ -69,11 +69,7 @@ __device__ __forceinline__ ImageRow image_row(const kgdet_head_targets &t, const
     h = t.valid_h[b];
     w = t.valid_w[b];
   }
-  ImageRow r;
-  r.n_gt = n;
-  r.vh = h > 0 ? min(h, t.H) : t.H;
-  r.vw = w > 0 ? min(w, t.W) : t.W;
-  return r;
+  return {n, extent_of(h, t.H), extent_of(w, t.W)};
 }
 
 }  // namespace
@@ -94,17 +90,14 @@ __global__ __launch_bounds__(256) void head_assign_select(const kgdet_head_targe
   const ImageRow im = image_row<TABLE>(t, table, cap, b);
   if (g >= im.n_gt) return;
   int *cand = reinterpret_cast<int *>(dist + N);
-  const float *box = t.gt_bboxes[b] + 4 * g;
-  // point_assigner.py:69-71: centre and size of the gt; :93-95: ((p - centre) / size).norm(dim=1)
-  const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2;
-  const float w = fmaxf(box[2] - box[0], 1e-6f), h = fmaxf(box[3] - box[1], 1e-6f);
+  const GtFrame gt = gt_frame(t.gt_bboxes[b] + 4 * g);
   if (tid == 0) { s_tbits = 0; s_count = 0; }
   // the image's valid extent (point_target_kp.py:107-118: the assigner only sees the points inside it)
   const int vh = im.vh, vw = im.vw;
   for (int i = tid; i < N; i += 256) {
     const int col = i % t.W, row = i / t.W;
     const float px = (float)col * t.stride, py = (float)row * t.stride;
-    const float dx = (px - cx) / w, dy = (py - cy) / h;
+    const float dx = (px - gt.cx) / gt.w, dy = (py - gt.cy) / gt.h;
     dist[i] = (row < vh && col < vw) ? sqrtf(dx * dx + dy * dy) : INFINITY;
   }
   __syncthreads();
@@ -112,8 +105,8 @@ __global__ __launch_bounds__(256) void head_assign_select(const kgdet_head_targe
   while (side * side < pos_num) ++side;
   float T = FLT_MAX;           // (every valid point is a candidate; invalid ones -- distance +inf -- never are)
   if (side <= vh && side <= vw) {
-    const int j0 = min(max((int)floorf(cx / t.stride + 0.5f) - side / 2, 0), vw - side);
-    const int i0 = min(max((int)floorf(cy / t.stride + 0.5f) - side / 2, 0), vh - side);
+    const int j0 = min(max((int)floorf(gt.cx / t.stride + 0.5f) - side / 2, 0), vw - side);
+    const int i0 = min(max((int)floorf(gt.cy / t.stride + 0.5f) - side / 2, 0), vh - side);
     for (int e = tid; e < side * side; e += 256)
       atomicMax(&s_tbits, __float_as_int(dist[(i0 + e / side) * t.W + j0 + e % side]));   // (distances are >= 0)
     __syncthreads();
@@ -156,11 +149,6 @@ __device__ __forceinline__ Row row_of(int r, int C, int K2) {
   return q;
 }
 
-struct PointCtx {
-  int a, label, nvis;      // assigned gt (0: none), its label, its number of visible keypoints
-  float px, py;
-};
-
 }  // namespace
 
 // block (tile of 64 points, channel group, image); 256 threads = 4 waves, lane = point, waves take rows round-robin.
@@ -172,7 +160,6 @@ __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t
                                                       const float *__restrict__ upstream, kgdet_head_maps grads,
                                                       const int32_t *__restrict__ table, int cap) {
   __shared__ int s_nvis[kMaxGt];
-  __shared__ float s_part[4][9];
   const int N = t.H * t.W, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = blockIdx.x * 64 + lane;
   const bool live = i < N;
@@ -182,31 +169,24 @@ __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t
   const int K = t.num_keypoints, K2 = 2 * K, C = t.num_classes;
   // visible keypoints per gt (kpt_weights.sum(1) / 2 of KP3:641-644)
   for (int g = wave; g < n_gt; g += 4) {
-    int cnt = 0;
-    for (int m = lane; m < K; m += 64) cnt += t.gt_keypoints[b][((long long)g * K + m) * 3 + 2] != 0.0f ? 1 : 0;
+    int cnt = visible_keypoints(t.gt_keypoints[b] + (long long)g * K * 3, K, lane, 64);
     for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d);
     if (lane == 0) s_nvis[g] = cnt;
   }
   __syncthreads();
-  PointCtx p;
-  p.a = final_assign(dsel, b, gmax, n_gt, N, ic);
-  p.label = p.a > 0 ? (t.gt_labels[b] ? (int)t.gt_labels[b][p.a - 1] : 1) : 0;
-  p.nvis = p.a > 0 ? s_nvis[p.a - 1] : 0;
-  p.px = (float)(ic % t.W) * t.stride;
-  p.py = (float)(ic / t.W) * t.stride;
-  const float *gbox = t.gt_bboxes[b] + 4 * max(p.a - 1, 0);
-  const float *gkp = t.gt_keypoints[b] + (long long)max(p.a - 1, 0) * K * 3;
-  const int vh = im.vh, vw = im.vw;
-  const bool inside = ic / t.W < vh && ic % t.W < vw;                // (a point outside is never assigned: p.a == 0)
-  const float label_w = p.a > 0 ? cfg.pos_weight : (inside ? 1.0f : 0.0f);   // point_target_kp.py:140-147, unmap fill 0
-  const float kp_w = p.nvis > 0 ? 1.0f / (float)(2 * p.nvis) * 4.0f : 0.0f;
+  const int a = final_assign(dsel, b, gmax, n_gt, N, ic);          // assigned gt (0: none)
+  const int nvis = a > 0 ? s_nvis[a - 1] : 0;
+  const float px = (float)(ic % t.W) * t.stride, py = (float)(ic / t.W) * t.stride;
+  const float *gbox = t.gt_bboxes[b] + 4 * max(a - 1, 0);
+  const float *gkp = t.gt_keypoints[b] + (long long)max(a - 1, 0) * K * 3;
+  const bool inside = ic / t.W < im.vh && ic % t.W < im.vw;          // (a point outside is never assigned: a == 0)
+  const PointLabel lab = point_label(t.gt_labels[b], a, inside, cfg.pos_weight);
+  const float kp_w = nvis > 0 ? 1.0f / (float)(2 * nvis) * 4.0f : 0.0f;     // (x 4: KP3:641-644)
   const float nt = cfg.normalize_term;
 
   float acc[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) acc[k] = 0.f;
-  float inv_total = 0.f;
-  if (BACKWARD) inv_total = 1.0f;   // (divided below: the reference divides the sum, then multiplies by loss_weight)
 
   const int total_rows = 3 * (C + 4 + K2);
   const int r_begin = blockIdx.y * rows_per_group, r_end = min(r_begin + rows_per_group, total_rows);
@@ -217,58 +197,45 @@ __global__ __launch_bounds__(256) void head_loss_rows(const kgdet_head_targets t
       const long long off = ((long long)b * C + q.c) * N + ic;
       const float x = maps.cls[q.stage][off];
       if (!BACKWARD) {
-        const float l = focal_fwd(x, p.label, q.c, cfg.gamma[q.stage], cfg.alpha[q.stage]) * label_w;
+        const float l = focal_fwd(x, lab.label, q.c, cfg.gamma[q.stage], cfg.alpha[q.stage]) * lab.weight;
         if (live) acc[k] += l;
       } else if (live) {
-        // loss = lw * (sum / num_total): d/dx = up * lw / num_total * w * focal'(x)
-        const float g = upstream[k] * cfg.loss_weight[k] / num_total_dev[0];
-        grads.cls[q.stage][off] = focal_bwd(x, p.label, q.c, cfg.gamma[q.stage], cfg.alpha[q.stage]) * label_w * g;
+        const float g = upstream[k] * cfg.loss_weight[k] / num_total_dev[0];      // loss = lw * (sum / num_total)
+        grads.cls[q.stage][off] = focal_bwd(x, lab.label, q.c, cfg.gamma[q.stage], cfg.alpha[q.stage]) * lab.weight * g;
       }
     } else {
       const float beta = cfg.beta[k - 3];
-      float pred_raw, centre, target, w;
+      float pred_raw, w;
       long long off;
-      if (q.kind == 1) {            // boxes: channels (x1, y1, x2, y2), offset_to_pts(y_first=False)
+      RowTarget ct;
+      if (q.kind == 1) {            // offset_to_pts(y_first=False)
         off = ((long long)b * 4 + q.c) * N + ic;
         pred_raw = maps.bbox[q.stage][off];
-        centre = (q.c & 1) ? p.py : p.px;
-        target = gbox[q.c];
-        w = p.a > 0 ? 1.0f : 0.0f;
-      } else {                      // keypoints: channel pairs are (y, x); the loss pairs them with (x, y) targets
+        ct = {(q.c & 1) ? py : px, gbox[q.c], true};
+        w = a > 0 ? 1.0f : 0.0f;
+      } else {
         off = ((long long)b * K2 + q.c) * N + ic;
         pred_raw = maps.kpt[q.stage][off];
-        const int m = q.c >> 1, is_x = q.c & 1;
-        centre = is_x ? p.px : p.py;
-        target = gkp[m * 3 + (is_x ? 0 : 1)];
-        w = (p.a > 0 && gkp[m * 3 + 2] != 0.0f) ? kp_w : 0.0f;
+        ct = keypoint_target(gkp, q.c, px, py);
+        w = (a > 0 && ct.on) ? kp_w : 0.0f;
       }
-      const float pred = pred_raw * t.stride + centre;
-      const float x = pred / nt - target / nt, diff = fabsf(x);      // csrc/smooth_l1.hip's expressions
+      const float pred = pred_raw * t.stride + ct.centre;            // offset_to_pts: pred * stride + centre
+      const float x = smooth_l1_x(pred, ct.target, nt);
       if (!BACKWARD) {
-        const float l = diff < beta ? 0.5f * diff * diff / beta : diff - 0.5f * beta;
+        const float diff = fabsf(x), l = smooth_l1_fwd(diff, beta, diff - 0.5f * beta);
         if (live && w != 0.0f) acc[k] += l * w;
       } else if (live) {
-        const float dl = diff < beta ? x / beta : (x > 0.0f ? 1.0f : x < 0.0f ? -1.0f : 0.0f);
         const float g = upstream[k] * cfg.loss_weight[k] / num_total_dev[0];
-        const float gr = w != 0.0f ? g * w * dl / nt * t.stride : 0.0f;
+        const float gr = smooth_l1_bwd(x, beta, w, g, nt, t.stride);
         if (q.kind == 1) grads.bbox[q.stage][off] = gr; else grads.kpt[q.stage][off] = gr;
       }
     }
   }
   if (!BACKWARD) {
-#pragma unroll
-    for (int k = 0; k < 9; ++k) {
-      float v = acc[k];
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) s_part[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < 9) {
-      const long long wg = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-      partial[wg * 9 + tid] = s_part[0][tid] + s_part[1][tid] + s_part[2][tid] + s_part[3][tid];
-    }
+    const float sum = block_sums(acc);
+    const long long wg = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (tid < 9) partial[wg * 9 + tid] = sum;
   }
-  (void)inv_total;
 }
 
 // one block: n_pos per image -> num_total; partials in fixed order; the nine losses
@@ -279,7 +246,6 @@ __global__ __launch_bounds__(256) void head_loss_finish(const kgdet_head_targets
                                                         const float *__restrict__ partial, int num_partials,
                                                         float *__restrict__ losses, float *__restrict__ num_total_out,
                                                         const int32_t *__restrict__ table, int cap) {
-  __shared__ float red[4][9];
   __shared__ int s_pos[4];
   __shared__ float s_total;
   const int N = t.H * t.W, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -301,162 +267,129 @@ __global__ __launch_bounds__(256) void head_loss_finish(const kgdet_head_targets
   for (int p = tid; p < num_partials; p += 256)
 #pragma unroll
     for (int k = 0; k < 9; ++k) acc[k] += partial[(long long)p * 9 + k];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    float v = acc[k];
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    if (lane == 0) red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < 9) {
-    const float s = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-    losses[tid] = cfg.loss_weight[tid] * (s / s_total);                  // losses/utils.py:44-48, focal_loss.py:76-82
-  }
+  const float s = block_sums(acc);                                        // (its barrier publishes s_total)
+  if (tid < 9) losses[tid] = cfg.loss_weight[tid] * (s / s_total);        // losses/utils.py:44-48, focal_loss.py:76-82
 }
 
 }  // namespace kgdet
 
 using namespace kgdet;
 
-extern "C" {
+namespace {
+
+// the launch shape and the workspace (the selections of the ABI first) of one descriptor; base == nullptr: for the size alone
+struct Plan {
+  int N, tiles;          // points per image, its 64-point tiles
+  int rows_per_group, groups;
+  float *dsel;           // [B][64][N]
+  float *partial;        // [B][groups][tiles][9]
+  size_t bytes;
+};
+Plan plan_of(const kgdet_head_targets *t, void *base) {
+  Plan p;
+  p.N = t->H * t->W;
+  p.tiles = ceil_div(p.N, 64);
+  p.rows_per_group = rows_per_group(3 * (t->num_classes + 4 + 2 * t->num_keypoints), p.tiles * t->B, 512, &p.groups);
+  p.bytes = 0;
+  p.dsel = take<float>(base, p.bytes, (size_t)t->B * kMaxGt * p.N);
+  p.partial = take<float>(base, p.bytes, (size_t)p.tiles * p.groups * t->B * 9);
+  p.bytes += 256;     // (the size the library has always named)
+  return p;
+}
 
 // by_table: the counts and extents live in device memory (the *_table entry points): the by-value fields are not looked at
-static int head_check(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, int *gmax, bool by_table = false) {
+int head_check(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, bool by_table, int *gmax) {
   KGDET_CHECK_SHAPE(t && cfg, "null descriptor");
-  KGDET_CHECK_SHAPE(t->B >= 1 && t->B <= kMaxImages, "1..%d images per call", kMaxImages);
+  if (int rc = check_targets(t, cfg->beta, 6, !by_table, gmax)) return rc;
   KGDET_CHECK_SHAPE(t->H > 0 && t->W > 0 && t->H * t->W <= kMaxPoints, "point grid beyond %d points", kMaxPoints);
-  KGDET_CHECK_SHAPE(t->num_classes > 0 && t->num_keypoints > 0, "bad channel counts");
   KGDET_CHECK_SHAPE(cfg->pos_num >= 1 && cfg->normalize_term > 0.0f, "bad assigner / normaliser");
-  for (int b = 0; b < t->B && !by_table; ++b) {
-    const int vh = t->valid_h[b] > 0 ? (t->valid_h[b] < t->H ? t->valid_h[b] : t->H) : t->H;
-    const int vw = t->valid_w[b] > 0 ? (t->valid_w[b] < t->W ? t->valid_w[b] : t->W) : t->W;
-    KGDET_CHECK_SHAPE(t->valid_h[b] >= 0 && t->valid_w[b] >= 0 && (long long)vh * vw >= cfg->pos_num,
+  KGDET_CHECK_SHAPE(cfg->pos_num <= t->H * t->W, "pos_num beyond the number of points");
+  for (int b = 0; b < t->B && !by_table; ++b)
+    KGDET_CHECK_SHAPE(t->valid_h[b] >= 0 && t->valid_w[b] >= 0 &&
+                          (long long)extent_of(t->valid_h[b], t->H) * extent_of(t->valid_w[b], t->W) >= cfg->pos_num,
                       "image %d: fewer valid points than pos_num", b);
-  }
-  int g = 0;
-  for (int b = 0; b < t->B; ++b) {
-    if (!by_table) {
-      KGDET_CHECK_SHAPE(t->num_gt[b] >= 1 && t->num_gt[b] <= kMaxGt, "image %d: %d ground-truth boxes (1..%d)", b,
-                        t->num_gt[b], kMaxGt);
-      if (t->num_gt[b] > g) g = t->num_gt[b];
-    }
-    KGDET_CHECK_SHAPE(t->gt_bboxes[b] && t->gt_keypoints[b], "null ground-truth pointer");
-  }
-  for (int k = 0; k < 6; ++k) KGDET_CHECK_SHAPE(cfg->beta[k] > 0.0f, "beta must be positive");
-  *gmax = g;
   return KGDET_OK;
 }
 
-static int head_table_check(const int32_t *table, int32_t gt_capacity) {
+int head_table_check(const int32_t *table, int32_t gt_capacity) {
   KGDET_CHECK_SHAPE(table != nullptr, "null target table");
   KGDET_CHECK_SHAPE(reinterpret_cast<uintptr_t>(table) % 16 == 0, "the target table must be 16-byte aligned");
   KGDET_CHECK_SHAPE(gt_capacity >= 1 && gt_capacity <= kMaxGt, "gt_capacity %d (1..%d)", gt_capacity, kMaxGt);
   return KGDET_OK;
 }
 
-static int head_rows_per_group(const kgdet_head_targets *t, int *groups) {
-  const int total_rows = 3 * (t->num_classes + 4 + 2 * t->num_keypoints);
-  // enough workgroups for the chip: tiles x groups x images ~ 512
-  const int tiles = ceil_div(t->H * t->W, 64);
-  int g = ceil_div(512, tiles * t->B);
-  if (g < 1) g = 1;
-  if (g > total_rows / 4) g = total_rows / 4 > 0 ? total_rows / 4 : 1;
-  const int rows = ceil_div(total_rows, g);
-  *groups = ceil_div(total_rows, rows);
-  return rows;
+// All four entry points.  `table` == nullptr is the by-value route (select grid = the largest count), else (gt_capacity, B)
+// workgroups.  Forward: select, rows, finish, writing `losses` and num_total.  Backward: the rows again, reading num_total and
+// `upstream` (the gradients of the nine losses) and writing `grads`.
+int head_run(bool backward, const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
+             const int32_t *table, int32_t gt_capacity, float *losses, const float *upstream, float *num_total,
+             const kgdet_head_maps *grads, void *workspace, size_t workspace_bytes, void *stream) {
+  const int cap = gt_capacity;
+  int gmax = 0;
+  if (int rc = head_check(t, cfg, table != nullptr, &gmax)) return rc;
+  if (table) gmax = cap;
+  KGDET_CHECK_SHAPE(maps && num_total && (backward ? upstream && grads : losses != nullptr), "null pointer");
+  for (int s = 0; s < 3; ++s)
+    KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s] &&
+                          (!backward || (grads->cls[s] && grads->bbox[s] && grads->kpt[s])),
+                      "null map");
+  const Plan p = plan_of(t, workspace);
+  if (int rc = check_workspace("head", workspace, workspace_bytes, p.bytes)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!backward) {
+    hipLaunchKernelGGL(table ? head_assign_select<true> : head_assign_select<false>, dim3(gmax, t->B), dim3(256),
+                       (size_t)p.N * 2 * sizeof(float), st, *t, cfg->pos_num, kMaxGt, p.dsel, table, cap);
+    KGDET_CHECK_LAUNCH("head_assign_select");
+  }
+  const auto rows = backward ? (table ? head_loss_rows<true, true> : head_loss_rows<true, false>)
+                             : (table ? head_loss_rows<false, true> : head_loss_rows<false, false>);
+  hipLaunchKernelGGL(rows, dim3(p.tiles, p.groups, t->B), dim3(256), 0, st, *t, *cfg, *maps, (const float *)p.dsel, kMaxGt,
+                     p.rows_per_group, backward ? nullptr : p.partial, backward ? (const float *)num_total : nullptr, upstream,
+                     backward ? *grads : kgdet_head_maps{}, table, cap);
+  KGDET_CHECK_LAUNCH(backward ? "head_loss_rows<backward>" : "head_loss_rows<forward>");
+  if (!backward) {
+    hipLaunchKernelGGL(table ? head_loss_finish<true> : head_loss_finish<false>, dim3(1), dim3(256), 0, st, *t, *cfg,
+                       (const float *)p.dsel, kMaxGt, (const float *)p.partial, p.tiles * p.groups * t->B, losses, num_total,
+                       table, cap);
+    KGDET_CHECK_LAUNCH("head_loss_finish");
+  }
+  return KGDET_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 size_t kgdet_head_loss_workspace_bytes(const kgdet_head_targets *t) {
-  if (t == nullptr) return 0;
-  int groups = 0;
-  head_rows_per_group(t, &groups);
-  const size_t N = (size_t)t->H * t->W, tiles = (N + 63) / 64;
-  return align_up((size_t)t->B * kMaxGt * N * sizeof(float), 256) + align_up(tiles * groups * t->B * 9 * sizeof(float), 256) +
-         256;
-}
-
-// both routes: `table` == nullptr is the by-value route (select grid = the largest count), else (gt_capacity, B) workgroups
-static int head_forward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
-                        const int32_t *table, int32_t cap, float *losses, float *num_total, void *workspace,
-                        size_t workspace_bytes, void *stream) {
-  int gmax = 0;
-  if (int rc = head_check(t, cfg, &gmax, table != nullptr)) return rc;
-  if (table) gmax = cap;
-  KGDET_CHECK_SHAPE(maps && losses && num_total, "null pointer");
-  for (int s = 0; s < 3; ++s) KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s], "null prediction map");
-  const size_t need = kgdet_head_loss_workspace_bytes(t);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("head_loss: needs %zu bytes of workspace (kgdet_head_loss_workspace_bytes), got %zu", need, workspace_bytes);
-    return KGDET_E_WORKSPACE;
-  }
-  const int N = t->H * t->W;
-  KGDET_CHECK_SHAPE(cfg->pos_num <= N, "pos_num beyond the number of points");
-  float *dsel = reinterpret_cast<float *>(workspace);
-  float *partial = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(workspace) +
-                                             align_up((size_t)t->B * kMaxGt * N * sizeof(float), 256));
-  hipLaunchKernelGGL(table ? head_assign_select<true> : head_assign_select<false>, dim3(gmax, t->B), dim3(256),
-                     (size_t)N * 2 * sizeof(float), (hipStream_t)stream, *t, cfg->pos_num, kMaxGt, dsel, table, (int)cap);
-  KGDET_CHECK_LAUNCH("head_assign_select");
-  int groups = 0;
-  const int rows = head_rows_per_group(t, &groups);
-  const int tiles = ceil_div(N, 64);
-  kgdet_head_maps none = {};
-  hipLaunchKernelGGL((table ? head_loss_rows<false, true> : head_loss_rows<false, false>), dim3(tiles, groups, t->B), dim3(256), 0, (hipStream_t)stream, *t, *cfg,
-                     *maps, dsel, kMaxGt, rows, partial, (const float *)nullptr, (const float *)nullptr, none, table, (int)cap);
-  KGDET_CHECK_LAUNCH("head_loss_rows<forward>");
-  hipLaunchKernelGGL(table ? head_loss_finish<true> : head_loss_finish<false>, dim3(1), dim3(256), 0, (hipStream_t)stream, *t, *cfg, dsel, kMaxGt, partial,
-                     tiles * groups * t->B, losses, num_total, table, (int)cap);
-  KGDET_CHECK_LAUNCH("head_loss_finish");
-  return KGDET_OK;
-}
-
-static int head_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
-                         const int32_t *table, int32_t cap, const float *grad_losses, const float *num_total,
-                         const kgdet_head_maps *grads, const void *workspace, size_t workspace_bytes, void *stream) {
-  int gmax = 0;
-  if (int rc = head_check(t, cfg, &gmax, table != nullptr)) return rc;
-  KGDET_CHECK_SHAPE(maps && grads && grad_losses && num_total, "null pointer");
-  for (int s = 0; s < 3; ++s)
-    KGDET_CHECK_SHAPE(maps->cls[s] && maps->bbox[s] && maps->kpt[s] && grads->cls[s] && grads->bbox[s] && grads->kpt[s],
-                      "null map");
-  const size_t need = kgdet_head_loss_workspace_bytes(t);
-  if (workspace == nullptr || workspace_bytes < need) {
-    set_error("head_loss: the forward call's workspace (the per-gt selections, %zu bytes) is needed, got %zu", need, workspace_bytes);
-    return KGDET_E_WORKSPACE;
-  }
-  const int N = t->H * t->W;
-  const float *dsel = reinterpret_cast<const float *>(workspace);
-  int groups = 0;
-  const int rows = head_rows_per_group(t, &groups);
-  hipLaunchKernelGGL((table ? head_loss_rows<true, true> : head_loss_rows<true, false>), dim3(ceil_div(N, 64), groups, t->B), dim3(256), 0, (hipStream_t)stream, *t,
-                     *cfg, *maps, dsel, kMaxGt, rows, (float *)nullptr, num_total, grad_losses, *grads, table, (int)cap);
-  KGDET_CHECK_LAUNCH("head_loss_rows<backward>");
-  return KGDET_OK;
+  return t ? plan_of(t, nullptr).bytes : 0;
 }
 
 int kgdet_head_loss_forward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
                             float *losses, float *num_total, void *workspace, size_t workspace_bytes, void *stream) {
-  return head_forward(t, cfg, maps, nullptr, 0, losses, num_total, workspace, workspace_bytes, stream);
+  return head_run(false, t, cfg, maps, nullptr, 0, losses, nullptr, num_total, nullptr, workspace, workspace_bytes, stream);
 }
 
+// (the backward calls only read num_total and the workspace)
 int kgdet_head_loss_backward(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
                              const float *grad_losses, const float *num_total, const kgdet_head_maps *grads,
                              const void *workspace, size_t workspace_bytes, void *stream) {
-  return head_backward(t, cfg, maps, nullptr, 0, grad_losses, num_total, grads, workspace, workspace_bytes, stream);
+  return head_run(true, t, cfg, maps, nullptr, 0, nullptr, grad_losses, const_cast<float *>(num_total), grads,
+                  const_cast<void *>(workspace), workspace_bytes, stream);
 }
 
 int kgdet_head_loss_forward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
                                   const int32_t *table, int32_t gt_capacity, float *losses, float *num_total, void *workspace,
                                   size_t workspace_bytes, void *stream) {
   if (int rc = head_table_check(table, gt_capacity)) return rc;
-  return head_forward(t, cfg, maps, table, gt_capacity, losses, num_total, workspace, workspace_bytes, stream);
+  return head_run(false, t, cfg, maps, table, gt_capacity, losses, nullptr, num_total, nullptr, workspace, workspace_bytes, stream);
 }
 
 int kgdet_head_loss_backward_table(const kgdet_head_targets *t, const kgdet_head_loss_cfg *cfg, const kgdet_head_maps *maps,
                                    const int32_t *table, int32_t gt_capacity, const float *grad_losses, const float *num_total,
                                    const kgdet_head_maps *grads, const void *workspace, size_t workspace_bytes, void *stream) {
   if (int rc = head_table_check(table, gt_capacity)) return rc;
-  return head_backward(t, cfg, maps, table, gt_capacity, grad_losses, num_total, grads, workspace, workspace_bytes, stream);
+  return head_run(true, t, cfg, maps, table, gt_capacity, nullptr, grad_losses, const_cast<float *>(num_total), grads,
+                  const_cast<void *>(workspace), workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -30,6 +30,9 @@
 //                         partials in fixed order per level.
 //
 // No tensor of targets or weights exists; nothing is read by the host.  Deterministic (fixed summation orders).
+// The loss rows' arithmetic, the PointAssigner frame of a gt, the reductions and the host-side skeleton are loss_math.h's, shared
+// with head_loss.hip; the selection rounds, the IoU assigner, the row enumeration, the decode order and the keypoint weight
+// are this file's.
 #include <float.h>
 
 #include "common.h"
@@ -43,15 +46,16 @@ namespace kgdet {
 
 namespace {
 
-constexpr int kMaxImages = KGDET_HEAD_MAX_IMAGES;
 constexpr int kMaxLevels = KGDET_SERIAL_MAX_LEVELS;
-constexpr int kMaxGt = 64;
 constexpr int kMaxPosNum = 64;
 constexpr int kMaxLevelPoints = 32768;
 constexpr int kFamilies = 5;   // cls, bbox_init, bbox_refine, kpt_init, kpt_refine
 
-// the workspace: the three tables of the ABI first
-struct Workspace {
+// the launch shape and the workspace (the three tables of the ABI first) of one descriptor; base == nullptr: for the size alone
+struct Plan {
+  int N;               // points per image
+  int tiles64, tiles256;
+  int rows_per_group, groups;
   int *a_init, *a_ref;
   float *best_iou;
   int *sel_idx;        // [B][64][pos_num] point index within the image (-1: none)
@@ -63,14 +67,7 @@ struct Workspace {
   size_t bytes;
 };
 
-struct Plan {
-  int N;               // points per image
-  int tiles64, tiles256, groups, rows_per_group;
-};
-
-int total_rows(const kgdet_serial_targets *t) { return t->num_classes + 8 + 4 * t->num_keypoints; }
-
-Plan plan_of(const kgdet_serial_targets *t) {
+Plan plan_of(const kgdet_serial_targets *t, int pos_num, void *base) {
   Plan p = {};
   for (int l = 0; l < t->L; ++l) {
     const int n = t->H[l] * t->W[l];
@@ -78,35 +75,18 @@ Plan plan_of(const kgdet_serial_targets *t) {
     p.tiles64 += ceil_div(n, 64);
     p.tiles256 += ceil_div(n, 256);
   }
-  // enough workgroups for the chip: tiles x groups x images ~ 2048
-  const int rows = total_rows(t);
-  int g = ceil_div(2048, p.tiles64 * t->B);
-  if (g > rows / 4) g = rows / 4 > 0 ? rows / 4 : 1;
-  p.rows_per_group = ceil_div(rows, g);
-  p.groups = ceil_div(rows, p.rows_per_group);
-  return p;
-}
-
-Workspace carve(const kgdet_serial_targets *t, int pos_num, const Plan &p, void *base) {
-  Workspace w = {};
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void *q = base ? static_cast<unsigned char *>(base) + off : nullptr;
-    off += align_up(bytes, 256);
-    return q;
-  };
+  p.rows_per_group = rows_per_group(t->num_classes + 8 + 4 * t->num_keypoints, p.tiles64 * t->B, 2048, &p.groups);
   const size_t BN = (size_t)t->B * p.N, BG = (size_t)t->B * kMaxGt;
-  w.a_init = static_cast<int *>(take(BN * 4));
-  w.a_ref = static_cast<int *>(take(BN * 4));
-  w.best_iou = static_cast<float *>(take(BN * 4));
-  w.sel_idx = static_cast<int *>(take(BG * pos_num * 4));
-  w.sel_dist = static_cast<float *>(take(BG * pos_num * 4));
-  w.gt_max = static_cast<int *>(take(BG * 4));
-  w.nvis = static_cast<int *>(take(BG * 4));
-  w.partial = static_cast<float *>(take((size_t)t->B * p.groups * p.tiles64 * kFamilies * 4));
-  w.counts = static_cast<int *>(take((size_t)t->B * p.tiles64 * 2 * 4));
-  w.bytes = off;
-  return w;
+  p.a_init = take<int>(base, p.bytes, BN);
+  p.a_ref = take<int>(base, p.bytes, BN);
+  p.best_iou = take<float>(base, p.bytes, BN);
+  p.sel_idx = take<int>(base, p.bytes, BG * pos_num);
+  p.sel_dist = take<float>(base, p.bytes, BG * pos_num);
+  p.gt_max = take<int>(base, p.bytes, BG);
+  p.nvis = take<int>(base, p.bytes, BG);
+  p.partial = take<float>(base, p.bytes, (size_t)t->B * p.groups * p.tiles64 * kFamilies);
+  p.counts = take<int>(base, p.bytes, (size_t)t->B * p.tiles64 * 2);
+  return p;
 }
 
 // tile -> (level, first point of the tile within the level, offset of the level within the image)
@@ -127,8 +107,6 @@ __device__ __forceinline__ Place place_of(const kgdet_serial_targets &t, int til
   }
   return q;
 }
-
-__device__ __forceinline__ int extent_of(int v, int full) { return v > 0 ? min(v, full) : full; }
 
 // geometry.py bbox_overlaps(gt, box), mode 'iou', in its order of operations
 __device__ __forceinline__ float iou_of(const float *__restrict__ g, float x1, float y1, float x2, float y2) {
@@ -173,15 +151,12 @@ __global__ __launch_bounds__(256) void serial_init_select(const kgdet_serial_tar
   __syncthreads();
   // visible keypoints (kpt_weights.sum(1) / 2 of reppoints_head_kp_serial.py loss_single)
   const int K = t.num_keypoints;
-  int cnt = 0;
-  for (int m = tid; m < K; m += 256) cnt += t.gt_keypoints[b][((long long)g * K + m) * 3 + 2] != 0.0f ? 1 : 0;
+  const int cnt = visible_keypoints(t.gt_keypoints[b] + (long long)g * K * 3, K, tid, 256);
   if (cnt) atomicAdd(&s_cnt, cnt);
-  const float *box = t.gt_bboxes[b] + 4 * g;
-  // point_assigner.py: centre, size, level of the gt; ((p - centre) / size).norm(dim=1)
-  const float cx = (box[0] + box[2]) / 2, cy = (box[1] + box[3]) / 2;
-  const float w = fmaxf(box[2] - box[0], 1e-6f), h = fmaxf(box[3] - box[1], 1e-6f);
+  const GtFrame gt = gt_frame(t.gt_bboxes[b] + 4 * g);
+  // point_assigner.py: the level of the gt
   const int lowest = (int)log2f(t.stride[0]);
-  int l = (int)((log2f(w / scale) + log2f(h / scale)) / 2) - lowest;
+  int l = (int)((log2f(gt.w / scale) + log2f(gt.h / scale)) / 2) - lowest;
   l = min(max(l, 0), t.L - 1);
   int level_off = 0;
   for (int k = 0; k < l; ++k) level_off += t.H[k] * t.W[k];
@@ -195,7 +170,7 @@ __global__ __launch_bounds__(256) void serial_init_select(const kgdet_serial_tar
     for (int i = tid; i < Nl; i += 256) {
       const int row = i / W, col = i - row * W;
       if (row >= vh || col >= vw) continue;
-      const float dx = ((float)col * s - cx) / w, dy = ((float)row * s - cy) / h;
+      const float dx = ((float)col * s - gt.cx) / gt.w, dy = ((float)row * s - gt.cy) / gt.h;
       const float d = sqrtf(dx * dx + dy * dy);
       const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)i;   // (distances are >= 0)
       if ((r == 0 || key > prev) && key < best) best = key;
@@ -307,7 +282,6 @@ __global__ __launch_bounds__(256) void serial_loss_rows(const kgdet_serial_targe
                                                         int *__restrict__ counts,
                                                         const float *__restrict__ num_total, const float *__restrict__ upstream,
                                                         kgdet_serial_maps grads) {
-  __shared__ float s_part[4][kFamilies];
   const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const Place q = place_of(t, blockIdx.x, 64);
   const int l = q.l, Nl = q.Nl, i = q.first + lane;
@@ -321,9 +295,7 @@ __global__ __launch_bounds__(256) void serial_loss_rows(const kgdet_serial_targe
   const int n_gt = t.num_gt[b];
   const int ai = live ? min(max(a_init[n], 0), n_gt) : 0, ar = live ? min(max(a_ref[n], -1), n_gt) : 0;
   const bool inside = row < extent_of(t.valid_h[b][l], t.H[l]) && col < extent_of(t.valid_w[b][l], W);
-  // point_target_kp.py: positives pos_weight, negatives 1, don't-care and (unmap fill) invalid points 0
-  const float label_w = ar > 0 ? cfg.pos_weight : ((ar == 0 && inside) ? 1.0f : 0.0f);
-  const int label = ar > 0 ? (t.gt_labels[b] ? (int)t.gt_labels[b][ar - 1] : 1) : 0;
+  const PointLabel lab = point_label(t.gt_labels[b], ar, inside, cfg.pos_weight);
   const unsigned long long pos_i = __ballot(ai > 0), pos_r = __ballot(ar > 0);
   const bool any_i = pos_i != 0, any_r = pos_r != 0;
   if (!BACKWARD && blockIdx.y == 0 && tid == 0) {        // the tile's positives, for num_total (serial_loss_finish)
@@ -344,12 +316,11 @@ __global__ __launch_bounds__(256) void serial_loss_rows(const kgdet_serial_targe
       const long long off = ((long long)b * C + r) * Nl + ic;
       const float x = maps.cls[l][off];
       if (!BACKWARD) {
-        const float v = focal_fwd(x, label, r, cfg.gamma, cfg.alpha) * label_w;
+        const float v = focal_fwd(x, lab.label, r, cfg.gamma, cfg.alpha) * lab.weight;
         if (live) acc[0] += v;
       } else if (live) {
-        // loss = lw * (sum / num_total): d/dx = up * lw / num_total * w * focal'(x)
-        const float g = upstream[0 * t.L + l] * cfg.loss_weight[0] / num_total[1];
-        grads.cls[l][off] = focal_bwd(x, label, r, cfg.gamma, cfg.alpha) * label_w * g;
+        const float g = upstream[0 * t.L + l] * cfg.loss_weight[0] / num_total[1];      // loss = lw * (sum / num_total)
+        grads.cls[l][off] = focal_bwd(x, lab.label, r, cfg.gamma, cfg.alpha) * lab.weight * g;
       }
       continue;
     }
@@ -360,53 +331,33 @@ __global__ __launch_bounds__(256) void serial_loss_rows(const kgdet_serial_targe
     const int a = init ? ai : ar;
     const long long off = ((long long)b * (box ? 4 : K2) + c) * Nl + ic;
     float *const *src = k == 1 ? maps.box_init : k == 2 ? maps.box_refine : k == 3 ? maps.kpt_init : maps.kpt_refine;
+    float *const *dst = k == 1 ? grads.box_init : k == 2 ? grads.box_refine : k == 3 ? grads.kpt_init : grads.kpt_refine;
     if (!(init ? any_i : any_r)) {                       // a tile without a positive of the stage: weight 0 throughout
-      if (BACKWARD && live) {
-        float *const *dst = k == 1 ? grads.box_init : k == 2 ? grads.box_refine : k == 3 ? grads.kpt_init : grads.kpt_refine;
-        dst[l][off] = 0.0f;
-      }
+      if (BACKWARD && live) dst[l][off] = 0.0f;
       continue;
     }
     const float pred_raw = src[l][off];
-    float centre, target, w;
-    if (box) {                     // channels (x1, y1, x2, y2)
-      centre = (c & 1) ? py : px;
-      target = t.gt_bboxes[b][4 * max(a - 1, 0) + c];
-      w = a > 0 ? 1.0f : 0.0f;
-    } else {                       // channel pairs are (y, x); the loss pairs them with (x, y) targets
-      const int m = c >> 1, is_x = c & 1;
-      const float *gkp = t.gt_keypoints[b] + ((long long)max(a - 1, 0) * K + m) * 3;
-      const int nv = a > 0 ? nvis[b * kMaxGt + a - 1] : 0;
-      centre = is_x ? px : py;
-      target = gkp[is_x ? 0 : 1];
-      w = (nv > 0 && gkp[2] != 0.0f) ? 1.0f / (float)(2 * nv) : 0.0f;     // (no x 4 here: reppoints_head_kp_serial.py)
-    }
+    const int gi = max(a - 1, 0), nv = (a > 0 && !box) ? nvis[b * kMaxGt + gi] : 0;
+    const RowTarget ct = box ? RowTarget{(c & 1) ? py : px, t.gt_bboxes[b][4 * gi + c], true}
+                             : keypoint_target(t.gt_keypoints[b] + (long long)gi * K * 3, c, px, py);
+    // (no x 4 on the keypoint weight here: reppoints_head_kp_serial.py)
+    const float w = box ? (a > 0 ? 1.0f : 0.0f) : ((nv > 0 && ct.on) ? 1.0f / (float)(2 * nv) : 0.0f);
     // boxes: centre + box * stride as the assigner saw it; keypoints: pred * stride + centre (offset_to_pts) -- the same sum
-    const float pred = centre + pred_raw * s;
-    const float x = pred / nt - target / nt, diff = fabsf(x);      // csrc/smooth_l1.hip's expressions
+    const float pred = ct.centre + pred_raw * s;
+    const float x = smooth_l1_x(pred, ct.target, nt);
     const float beta = cfg.beta[k - 1];
     if (!BACKWARD) {
-      const float v = diff < beta ? 0.5f * diff * diff / beta : diff - 0.5f * beta;
+      const float diff = fabsf(x), v = smooth_l1_fwd(diff, beta, diff - 0.5f * beta);
       if (live && w != 0.0f) acc[k] += v * w;
     } else if (live) {
-      const float dl = diff < beta ? x / beta : (x > 0.0f ? 1.0f : x < 0.0f ? -1.0f : 0.0f);
       const float g = upstream[k * t.L + l] * cfg.loss_weight[k] / num_total[init ? 0 : 1];
-      float *const *dst = k == 1 ? grads.box_init : k == 2 ? grads.box_refine : k == 3 ? grads.kpt_init : grads.kpt_refine;
-      dst[l][off] = w != 0.0f ? g * w * dl / nt * s : 0.0f;
+      dst[l][off] = smooth_l1_bwd(x, beta, w, g, nt, s);
     }
   }
   if (!BACKWARD) {
-#pragma unroll
-    for (int k = 0; k < kFamilies; ++k) {
-      float v = acc[k];
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) s_part[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid < kFamilies) {
-      const long long wg = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-      partial[wg * kFamilies + tid] = s_part[0][tid] + s_part[1][tid] + s_part[2][tid] + s_part[3][tid];
-    }
+    const float sum = block_sums(acc);
+    const long long wg = ((long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+    if (tid < kFamilies) partial[wg * kFamilies + tid] = sum;
   }
 }
 
@@ -415,7 +366,6 @@ __global__ __launch_bounds__(256) void serial_loss_finish(const kgdet_serial_tar
                                                           int tiles64, int groups, const int *__restrict__ counts,
                                                           const float *__restrict__ partial,
                                                           float *__restrict__ losses, float *__restrict__ num_total_out) {
-  __shared__ float red[4][kFamilies];
   __shared__ int s_pos[4][2];
   __shared__ float s_total[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -449,16 +399,9 @@ __global__ __launch_bounds__(256) void serial_loss_finish(const kgdet_serial_tar
 #pragma unroll
       for (int k = 0; k < kFamilies; ++k) acc[k] += partial[wg * kFamilies + k];
     }
-    __syncthreads();                                       // (red of the previous level has been read; s_total is written)
-#pragma unroll
-    for (int k = 0; k < kFamilies; ++k) {
-      float v = acc[k];
-      for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-      if (lane == 0) red[wave][k] = v;
-    }
-    __syncthreads();
+    __syncthreads();                                       // (the previous level's sums have been read; s_total is written)
+    const float sum = block_sums(acc);
     if (tid < kFamilies) {
-      const float sum = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
       const bool init = tid == 1 || tid == 3;
       losses[tid * t.L + l] = cfg.loss_weight[tid] * (sum / s_total[init ? 0 : 1]);    // losses/utils.py, focal_loss.py
     }
@@ -470,13 +413,12 @@ __global__ __launch_bounds__(256) void serial_loss_finish(const kgdet_serial_tar
 
 using namespace kgdet;
 
-extern "C" {
+namespace {
 
-static int serial_check(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, int *gmax) {
+int serial_check(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, int *gmax) {
   KGDET_CHECK_SHAPE(t && cfg, "null descriptor");
-  KGDET_CHECK_SHAPE(t->B >= 1 && t->B <= kMaxImages, "1..%d images per call", kMaxImages);
   KGDET_CHECK_SHAPE(t->L >= 1 && t->L <= kMaxLevels, "1..%d pyramid levels", kMaxLevels);
-  KGDET_CHECK_SHAPE(t->num_classes > 0 && t->num_keypoints > 0, "bad channel counts");
+  if (int rc = check_targets(t, cfg->beta, 4, true, gmax)) return rc;
   KGDET_CHECK_SHAPE(cfg->pos_num >= 1 && cfg->pos_num <= kMaxPosNum, "pos_num 1..%d", kMaxPosNum);
   KGDET_CHECK_SHAPE(cfg->scale > 0.0f && cfg->point_base_scale > 0.0f, "bad assigner scale / normaliser");
   for (int l = 0; l < t->L; ++l) {
@@ -486,26 +428,15 @@ static int serial_check(const kgdet_serial_targets *t, const kgdet_serial_loss_c
     const float m = frexpf(t->stride[l], &e);
     KGDET_CHECK_SHAPE(t->stride[l] >= 1.0f && m == 0.5f && (l == 0 || t->stride[l] == 2.0f * t->stride[l - 1]),
                       "strides must be consecutive powers of two");
+    for (int b = 0; b < t->B; ++b)
+      KGDET_CHECK_SHAPE(t->valid_h[b][l] >= 0 && t->valid_w[b][l] >= 0 &&
+                            (long long)extent_of(t->valid_h[b][l], t->H[l]) * extent_of(t->valid_w[b][l], t->W[l]) >= cfg->pos_num,
+                        "image %d, level %d: fewer valid points than pos_num", b, l);
   }
-  int g = 0;
-  for (int b = 0; b < t->B; ++b) {
-    KGDET_CHECK_SHAPE(t->num_gt[b] >= 1 && t->num_gt[b] <= kMaxGt, "image %d: %d ground-truth boxes (1..%d)", b, t->num_gt[b],
-                      kMaxGt);
-    KGDET_CHECK_SHAPE(t->gt_bboxes[b] && t->gt_keypoints[b], "null ground-truth pointer");
-    if (t->num_gt[b] > g) g = t->num_gt[b];
-    for (int l = 0; l < t->L; ++l) {
-      KGDET_CHECK_SHAPE(t->valid_h[b][l] >= 0 && t->valid_w[b][l] >= 0, "negative valid extent");
-      const int vh = t->valid_h[b][l] > 0 && t->valid_h[b][l] < t->H[l] ? t->valid_h[b][l] : t->H[l];
-      const int vw = t->valid_w[b][l] > 0 && t->valid_w[b][l] < t->W[l] ? t->valid_w[b][l] : t->W[l];
-      KGDET_CHECK_SHAPE((long long)vh * vw >= cfg->pos_num, "image %d, level %d: fewer valid points than pos_num", b, l);
-    }
-  }
-  for (int k = 0; k < 4; ++k) KGDET_CHECK_SHAPE(cfg->beta[k] > 0.0f, "beta must be positive");
-  *gmax = g;
   return KGDET_OK;
 }
 
-static int serial_maps_check(const kgdet_serial_targets *t, const kgdet_serial_maps *m, const char *what) {
+int serial_maps_check(const kgdet_serial_targets *t, const kgdet_serial_maps *m, const char *what) {
   KGDET_CHECK_SHAPE(m, "null %s descriptor", what);
   for (int l = 0; l < t->L; ++l)
     KGDET_CHECK_SHAPE(m->cls[l] && m->box_init[l] && m->box_refine[l] && m->kpt_init[l] && m->kpt_refine[l], "null %s (level %d)",
@@ -513,63 +444,66 @@ static int serial_maps_check(const kgdet_serial_targets *t, const kgdet_serial_m
   return KGDET_OK;
 }
 
+// Both entry points.  Forward: select, IoU, assign, rows, finish, writing `losses` and num_total.  Backward: the rows again,
+// reading num_total and `upstream` (the gradients of the 5 * L losses) and writing `grads`.
+int serial_run(bool backward, const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, const kgdet_serial_maps *maps,
+               float *losses, const float *upstream, float *num_total, const kgdet_serial_maps *grads, void *workspace,
+               size_t workspace_bytes, void *stream) {
+  int gmax = 0;
+  if (int rc = serial_check(t, cfg, &gmax)) return rc;
+  if (int rc = serial_maps_check(t, maps, "prediction map")) return rc;
+  if (backward)
+    if (int rc = serial_maps_check(t, grads, "gradient map")) return rc;
+  KGDET_CHECK_SHAPE(num_total && (backward ? upstream != nullptr : losses != nullptr), "null pointer");
+  const Plan p = plan_of(t, cfg->pos_num, workspace);
+  if (int rc = check_workspace("serial", workspace, workspace_bytes, p.bytes)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (!backward) {
+    hipLaunchKernelGGL(serial_init_select, dim3(gmax, t->B), dim3(256), 0, st, *t, cfg->pos_num, cfg->scale, p.sel_idx,
+                       p.sel_dist, p.gt_max, p.nvis);
+    KGDET_CHECK_LAUNCH("serial_init_select");
+    hipLaunchKernelGGL(serial_refine_iou, dim3(p.tiles256, t->B), dim3(256), 0, st, *t, *cfg, *maps, p.N, p.a_init, p.a_ref,
+                       p.best_iou, p.gt_max);
+    KGDET_CHECK_LAUNCH("serial_refine_iou");
+    hipLaunchKernelGGL(serial_assign_finish, dim3(p.tiles256 + 1, t->B), dim3(256), 0, st, *t, *cfg, *maps, p.N, p.tiles256,
+                       (const int *)p.sel_idx, (const float *)p.sel_dist, (const int *)p.gt_max, p.a_init, p.a_ref);
+    KGDET_CHECK_LAUNCH("serial_assign_finish");
+  }
+  hipLaunchKernelGGL(backward ? serial_loss_rows<true> : serial_loss_rows<false>, dim3(p.tiles64, p.groups, t->B),
+                     dim3(256), 0, st, *t, *cfg, *maps, p.N, p.rows_per_group, (const int *)p.a_init, (const int *)p.a_ref,
+                     (const int *)p.nvis, backward ? nullptr : p.partial, backward ? nullptr : p.counts,
+                     backward ? (const float *)num_total : nullptr, upstream,
+                     backward ? *grads : kgdet_serial_maps{});
+  KGDET_CHECK_LAUNCH(backward ? "serial_loss_rows<backward>" : "serial_loss_rows<forward>");
+  if (!backward) {
+    hipLaunchKernelGGL(serial_loss_finish, dim3(1), dim3(256), 0, st, *t, *cfg, p.tiles64, p.groups, (const int *)p.counts,
+                       (const float *)p.partial, losses, num_total);
+    KGDET_CHECK_LAUNCH("serial_loss_finish");
+  }
+  return KGDET_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
 size_t kgdet_serial_loss_workspace_bytes(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg) {
   int gmax = 0;
   if (serial_check(t, cfg, &gmax)) return 0;
-  return carve(t, cfg->pos_num, plan_of(t), nullptr).bytes;
+  return plan_of(t, cfg->pos_num, nullptr).bytes;
 }
 
 int kgdet_serial_loss_forward(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, const kgdet_serial_maps *maps,
                               float *losses, float *num_total, void *workspace, size_t workspace_bytes, void *stream) {
-  int gmax = 0;
-  if (int rc = serial_check(t, cfg, &gmax)) return rc;
-  if (int rc = serial_maps_check(t, maps, "prediction map")) return rc;
-  KGDET_CHECK_SHAPE(losses && num_total, "null pointer");
-  const Plan p = plan_of(t);
-  const Workspace w = carve(t, cfg->pos_num, p, workspace);
-  if (workspace == nullptr || workspace_bytes < w.bytes) {
-    set_error("serial_loss: needs %zu bytes of workspace (kgdet_serial_loss_workspace_bytes), got %zu", w.bytes, workspace_bytes);
-    return KGDET_E_WORKSPACE;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(serial_init_select, dim3(gmax, t->B), dim3(256), 0, st, *t, cfg->pos_num, cfg->scale, w.sel_idx, w.sel_dist,
-                     w.gt_max, w.nvis);
-  KGDET_CHECK_LAUNCH("serial_init_select");
-  hipLaunchKernelGGL(serial_refine_iou, dim3(p.tiles256, t->B), dim3(256), 0, st, *t, *cfg, *maps, p.N, w.a_init, w.a_ref,
-                     w.best_iou, w.gt_max);
-  KGDET_CHECK_LAUNCH("serial_refine_iou");
-  hipLaunchKernelGGL(serial_assign_finish, dim3(p.tiles256 + 1, t->B), dim3(256), 0, st, *t, *cfg, *maps, p.N, p.tiles256,
-                     w.sel_idx, w.sel_dist, w.gt_max, w.a_init, w.a_ref);
-  KGDET_CHECK_LAUNCH("serial_assign_finish");
-  kgdet_serial_maps none = {};
-  hipLaunchKernelGGL(serial_loss_rows<false>, dim3(p.tiles64, p.groups, t->B), dim3(256), 0, st, *t, *cfg, *maps, p.N,
-                     p.rows_per_group, w.a_init, w.a_ref, w.nvis, w.partial, w.counts, (const float *)nullptr, (const float *)nullptr, none);
-  KGDET_CHECK_LAUNCH("serial_loss_rows<forward>");
-  hipLaunchKernelGGL(serial_loss_finish, dim3(1), dim3(256), 0, st, *t, *cfg, p.tiles64, p.groups, w.counts, w.partial,
-                     losses, num_total);
-  KGDET_CHECK_LAUNCH("serial_loss_finish");
-  return KGDET_OK;
+  return serial_run(false, t, cfg, maps, losses, nullptr, num_total, nullptr, workspace, workspace_bytes, stream);
 }
 
+// (the backward call only reads num_total and the workspace)
 int kgdet_serial_loss_backward(const kgdet_serial_targets *t, const kgdet_serial_loss_cfg *cfg, const kgdet_serial_maps *maps,
                                const float *grad_losses, const float *num_total, const kgdet_serial_maps *grads,
                                const void *workspace, size_t workspace_bytes, void *stream) {
-  int gmax = 0;
-  if (int rc = serial_check(t, cfg, &gmax)) return rc;
-  if (int rc = serial_maps_check(t, maps, "prediction map")) return rc;
-  if (int rc = serial_maps_check(t, grads, "gradient map")) return rc;
-  KGDET_CHECK_SHAPE(grad_losses && num_total, "null pointer");
-  const Plan p = plan_of(t);
-  const Workspace w = carve(t, cfg->pos_num, p, const_cast<void *>(workspace));
-  if (workspace == nullptr || workspace_bytes < w.bytes) {
-    set_error("serial_loss: the forward call's workspace (the assignments, %zu bytes) is needed, got %zu", w.bytes,
-              workspace_bytes);
-    return KGDET_E_WORKSPACE;
-  }
-  hipLaunchKernelGGL(serial_loss_rows<true>, dim3(p.tiles64, p.groups, t->B), dim3(256), 0, (hipStream_t)stream, *t, *cfg, *maps,
-                     p.N, p.rows_per_group, w.a_init, w.a_ref, w.nvis, (float *)nullptr, (int *)nullptr, num_total, grad_losses, *grads);
-  KGDET_CHECK_LAUNCH("serial_loss_rows<backward>");
-  return KGDET_OK;
+  return serial_run(true, t, cfg, maps, nullptr, grad_losses, const_cast<float *>(num_total), grads,
+                    const_cast<void *>(workspace), workspace_bytes, stream);
 }
 
 }  // extern "C"

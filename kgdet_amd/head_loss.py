@@ -10,6 +10,9 @@ tables, without materialising a target or weight tensor and without a host read.
 
 ``KGDET_FUSED_HEAD_LOSS=0`` selects the torch chain (A/B, and what the parity tests compare against).
 
+What the wrapper of the serial / parallel heads' fused loss (``serial_loss.py``) needs as well lives here once: the ground-truth
+check, the ground-truth pointers of a targets descriptor, and the ``autograd.Function`` around a forward / backward call pair.
+
 The table route (``gt_table`` / ``gt_capacity``): the per-image ground-truth counts and valid extents are read from a device
 table [B, 4] int32 = (num_gt, valid_h, valid_w, 0) when the kernels run, and every ground-truth tensor is a buffer of
 ``gt_capacity`` rows of which the first ``num_gt`` count -- the launch arguments no longer depend on the batch
@@ -23,7 +26,7 @@ import torch
 from . import _lib
 
 ENABLED = os.environ.get('KGDET_FUSED_HEAD_LOSS', '1') == '1'
-MAX_IMAGES, MAX_GT, MAX_POINTS = 16, 64, 4096
+MAX_IMAGES, MAX_GT, MAX_POINTS = 16, 64, 4096            # MAX_IMAGES, MAX_GT: both loss families' (csrc/loss_math.h)
 
 
 class HeadTargets(ctypes.Structure):
@@ -51,6 +54,86 @@ def _maps(tensors):
     return m
 
 
+# ---- shared with serial_loss.py: the ground-truth check, the ground-truth pointers, the autograd.Function of a call pair
+def gt_why_not(B, device, num_keypts, gt_bboxes, gt_labels, gt_keypoints, cap=None):
+    """None when the kernels can take the ground truth of ``B`` images for maps on ``device``, else the reason in words.
+    ``cap``: the table route -- every tensor is a buffer of at least ``cap`` rows, and the counts are not the host's to check."""
+    for b in range(B):
+        g = gt_bboxes[b].shape[0]
+        if cap is not None:
+            if g < cap or gt_keypoints[b].shape[0] < cap or gt_labels[b].shape[0] < cap:
+                return 'image %d: a ground-truth buffer is shorter than the capacity of %d rows' % (b, cap)
+        elif g < 1 or g > MAX_GT:
+            return 'image %d: %d ground truths (1..%d)' % (b, g, MAX_GT)
+        if gt_bboxes[b].dtype != torch.float32 or gt_keypoints[b].dtype != torch.float32 or \
+                gt_keypoints[b].shape[1:] != (num_keypts, 3):
+            return 'image %d: ground truth that is not float32 [n, 4] and [n, %d, 3]' % (b, num_keypts)
+        # the kernels dereference the raw ground-truth pointers: they must live on the maps' device (CPU-resident or
+        # other-GPU ground truth takes the torch chain, which raises torch's own device-mismatch error or works)
+        if gt_bboxes[b].device != device or gt_keypoints[b].device != device:
+            return 'image %d: ground truth on another device than the maps' % b
+        if gt_labels is not None and gt_labels[b] is not None and (gt_labels[b].dtype != torch.int64 or
+                                                                   gt_labels[b].device != device):
+            return 'image %d: labels that are not int64 on the maps\' device' % b
+    return None
+
+
+def fill_ground_truth(t, gt_bboxes, gt_labels, gt_keypoints, counts=True):
+    """the ground-truth pointers of the ``t.B`` images (with ``counts``: and ``num_gt``) of a targets descriptor; returns the
+    contiguous tensors the pointers refer to, which must outlive the calls"""
+    keep = []
+    for b in range(t.B):
+        bb, kp = gt_bboxes[b].contiguous(), gt_keypoints[b].contiguous()
+        if bb.shape[0] == 0:
+            raise ValueError('No gt or bboxes')
+        lab = None if gt_labels is None or gt_labels[b] is None else gt_labels[b].contiguous()
+        keep += [bb, kp, lab]
+        if counts:
+            t.num_gt[b] = bb.shape[0]
+        t.gt_bboxes[b], t.gt_keypoints[b] = bb.data_ptr(), kp.data_ptr()
+        t.gt_labels[b] = lab.data_ptr() if lab is not None else None
+    return keep
+
+
+def bind(fn, targets, cfg, *extra):
+    """a library call of either family as ``call(maps descriptor, *rest)``: fn(targets, cfg, maps, *extra, *rest), status checked"""
+    def call(hm, *rest):
+        _lib.check(fn(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm), *extra, *rest), fn.__name__)
+    return call
+
+
+class FusedLoss(torch.autograd.Function):
+    """``apply(forward, backward, ws_bytes, n, describe, keep, *maps)`` -> ``n`` 0-dim losses.  ``forward`` / ``backward``: the two
+    library calls (``bind``); ``describe``: tensors -> maps descriptor; ``keep``: whatever the descriptors point at."""
+
+    @staticmethod
+    def forward(ctx, forward, backward, ws_bytes, n, describe, keep, *maps):
+        maps = tuple(m.contiguous() for m in maps)
+        dev = maps[0].device
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        # the losses, then num_total: two floats for the serial heads, one (and an unused slot) for the KGDet head
+        out = torch.empty(n + 2, dtype=torch.float32, device=dev)
+        forward(describe(maps), _lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 4 * n), _lib.ptr(ws), ctypes.c_size_t(ws_bytes),
+                _lib.current_stream())
+        ctx.call = (backward, ws_bytes, n, describe, keep, ws, out)
+        ctx.save_for_backward(*maps)
+        return tuple(out[k] for k in range(n))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grad_losses):
+        maps = ctx.saved_tensors
+        backward, ws_bytes, n, describe, _, ws, out = ctx.call
+        zero = torch.zeros((), dtype=torch.float32, device=maps[0].device) if any(g is None for g in grad_losses) else None
+        up = torch.stack([(zero if g is None else g).reshape(()).float() for g in grad_losses])
+        grads = tuple(torch.empty_like(m) for m in maps)
+        hg = describe(grads)
+        backward(describe(maps), _lib.ptr(up), ctypes.c_void_p(out.data_ptr() + 4 * n), ctypes.byref(hg), _lib.ptr(ws),
+                 ctypes.c_size_t(ws_bytes), _lib.current_stream())
+        return (None,) * 6 + grads
+
+
+# ---- the KGDet head
 def applicable(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, gt_bboxes_ignore,
                all_valid=True, valid_sizes=None, gt_table=None, gt_capacity=None):
     """the fused kernels cover exactly the case ``points.dense_targets_applicable`` covers for one level, on the GPU, in
@@ -104,78 +187,7 @@ def why_not(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, 
             return 'the table is not a contiguous int32 [%d, 4] tensor on the maps\' device' % B
         if gt_labels is None or any(l is None for l in gt_labels):
             return 'the table route needs label buffers'
-    for b in range(B):
-        g = gt_bboxes[b].shape[0]
-        if cap is not None:
-            if g < cap or gt_keypoints[b].shape[0] < cap or gt_labels[b].shape[0] < cap:
-                return 'image %d: a ground-truth buffer is shorter than the capacity of %d rows' % (b, cap)
-        elif g < 1 or g > MAX_GT:
-            return 'image %d: %d ground truths (1..%d)' % (b, g, MAX_GT)
-        if gt_bboxes[b].dtype != torch.float32 or gt_keypoints[b].dtype != torch.float32 or \
-                gt_keypoints[b].shape[1:] != (head.num_keypts, 3):
-            return 'image %d: ground truth that is not float32 [n, 4] and [n, %d, 3]' % (b, head.num_keypts)
-        # the kernels dereference the raw ground-truth pointers: they must live on the maps' device (CPU-resident or
-        # other-GPU ground truth takes the torch chain, which raises torch's own device-mismatch error or works)
-        if gt_bboxes[b].device != t0.device or gt_keypoints[b].device != t0.device:
-            return 'image %d: ground truth on another device than the maps' % b
-        if gt_labels is not None and gt_labels[b] is not None and (gt_labels[b].dtype != torch.int64 or
-                                                                   gt_labels[b].device != t0.device):
-            return 'image %d: labels that are not int64 on the maps\' device' % b
-    return None
-
-
-class _HeadLoss(torch.autograd.Function):
-    """(cls_1..3, bbox_1..3, kpt_1..3 prediction maps) -> nine 0-dim losses"""
-
-    @staticmethod
-    def forward(ctx, targets, cfg, keep, table, cap, *maps):
-        L = _lib.lib()
-        maps = tuple(m.contiguous() for m in maps)
-        dev = maps[0].device
-        ws_bytes = L.kgdet_head_loss_workspace_bytes(ctypes.byref(targets))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        out = torch.empty(10, dtype=torch.float32, device=dev)          # nine losses + num_total
-        hm = _maps(maps)
-        tail = (_lib.ptr(out), ctypes.c_void_p(out.data_ptr() + 36), _lib.ptr(ws), ctypes.c_size_t(ws_bytes),
-                _lib.current_stream())
-        if table is None:
-            _lib.check(L.kgdet_head_loss_forward(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm), *tail),
-                       'kgdet_head_loss_forward')
-        else:
-            _lib.check(L.kgdet_head_loss_forward_table(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm),
-                                                       _lib.ptr(table), ctypes.c_int32(cap), *tail),
-                       'kgdet_head_loss_forward_table')
-        ctx.targets, ctx.cfg, ctx.keep, ctx.ws, ctx.ws_bytes, ctx.out = targets, cfg, keep, ws, ws_bytes, out
-        ctx.table, ctx.cap = table, cap
-        ctx.save_for_backward(*maps)
-        return tuple(out[k] for k in range(9))
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grad_losses):
-        maps = ctx.saved_tensors
-        dev = maps[0].device
-        zero = None
-        gl = []
-        for g in grad_losses:
-            if g is None:
-                if zero is None:
-                    zero = torch.zeros((), dtype=torch.float32, device=dev)
-                g = zero
-            gl.append(g.reshape(()).float())
-        up = torch.stack(gl)
-        grads = tuple(torch.empty_like(m) for m in maps)
-        hm, hg = _maps(maps), _maps(grads)
-        tail = (_lib.ptr(up), ctypes.c_void_p(ctx.out.data_ptr() + 36), ctypes.byref(hg), _lib.ptr(ctx.ws),
-                ctypes.c_size_t(ctx.ws_bytes), _lib.current_stream())
-        if ctx.table is None:
-            _lib.check(_lib.lib().kgdet_head_loss_backward(
-                ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), *tail), 'kgdet_head_loss_backward')
-        else:
-            _lib.check(_lib.lib().kgdet_head_loss_backward_table(
-                ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), _lib.ptr(ctx.table),
-                ctypes.c_int32(ctx.cap), *tail), 'kgdet_head_loss_backward_table')
-        return (None, None, None, None, None) + grads
+    return gt_why_not(B, t0.device, head.num_keypts, gt_bboxes, gt_labels, gt_keypoints, cap)
 
 
 def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels, gt_keypoints, valid_sizes=None,
@@ -189,19 +201,10 @@ def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels
     t = HeadTargets()
     t.B, t.H, t.W, t.num_classes, t.num_keypoints = B, H, W, C, head.num_keypts
     t.stride = float(head.point_strides[0])
-    keep = []                                    # the contiguous ground-truth tensors the pointers refer to
-    for b in range(B):
-        bb, kp = gt_bboxes[b].contiguous(), gt_keypoints[b].contiguous()
-        if bb.shape[0] == 0:
-            raise ValueError('No gt or bboxes')
-        lab = None if gt_labels is None or gt_labels[b] is None else gt_labels[b].contiguous()
-        keep += [bb, kp, lab]
-        if gt_table is None:
-            t.num_gt[b] = bb.shape[0]
-        if valid_sizes is not None and gt_table is None:
+    keep = fill_ground_truth(t, gt_bboxes, gt_labels, gt_keypoints, counts=gt_table is None)
+    if valid_sizes is not None and gt_table is None:
+        for b in range(B):
             t.valid_h[b], t.valid_w[b] = int(valid_sizes[b][0]), int(valid_sizes[b][1])
-        t.gt_bboxes[b], t.gt_keypoints[b] = bb.data_ptr(), kp.data_ptr()
-        t.gt_labels[b] = lab.data_ptr() if lab is not None else None
     c = HeadLossCfg()
     a = cfg.assigner
     c.pos_num = int(a.get('pos_num', 3))
@@ -214,7 +217,13 @@ def head_loss(head, cfg, cls_scores, kpt_preds, bbox_preds, gt_bboxes, gt_labels
         c.loss_weight[s], c.loss_weight[3 + s], c.loss_weight[6 + s] = float(lc.loss_weight), float(lb.loss_weight), \
             float(lk.loss_weight)
     maps = [cls_scores[s][0] for s in range(3)] + [bbox_preds[s][0] for s in range(3)] + [kpt_preds[s][0] for s in range(3)]
-    out = _HeadLoss.apply(t, c, keep, gt_table, cap, *maps)
+    L = _lib.lib()
+    if gt_table is None:
+        calls = bind(L.kgdet_head_loss_forward, t, c), bind(L.kgdet_head_loss_backward, t, c)
+    else:
+        table = (_lib.ptr(gt_table), ctypes.c_int32(cap))
+        calls = bind(L.kgdet_head_loss_forward_table, t, c, *table), bind(L.kgdet_head_loss_backward_table, t, c, *table)
+    out = FusedLoss.apply(*calls, L.kgdet_head_loss_workspace_bytes(ctypes.byref(t)), 9, _maps, (keep, gt_table), *maps)
     names = ['loss_cls_1', 'loss_cls_2', 'loss_cls_3', 'loss_bbox_1', 'loss_bbox_2', 'loss_bbox_3',
              'loss_kpt_1', 'loss_kpt_2', 'loss_kpt_3']
     return {n: [v] for n, v in zip(names, out)}

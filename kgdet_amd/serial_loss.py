@@ -9,7 +9,8 @@ regions, sigmoid focal + smooth-L1 losses with ``reduction='mean'`` -- this modu
 gradients of the 5 x L maps from the raw prediction maps, the two box maps of ``moment.moment_bbox`` and the ground-truth
 tables, without materialising a target or weight tensor and without a host read.
 
-``KGDET_FUSED_SERIAL_LOSS=0`` selects the torch chain (A/B, and what the parity tests compare against).
+``KGDET_FUSED_SERIAL_LOSS=0`` selects the torch chain (A/B, and what the parity tests compare against).  The ``autograd.Function``
+skeleton, the ground-truth pointers and the ground-truth check are ``head_loss.py``'s.
 """
 import ctypes
 import os
@@ -18,9 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from .head_loss import MAX_IMAGES, FusedLoss, bind, fill_ground_truth, gt_why_not
 
 ENABLED = os.environ.get('KGDET_FUSED_SERIAL_LOSS', '1') == '1'
-MAX_IMAGES, MAX_GT, MAX_LEVELS, MAX_LEVEL_POINTS, MAX_POS_NUM = 16, 64, 8, 32768, 64
+MAX_LEVELS, MAX_LEVEL_POINTS, MAX_POS_NUM = 8, 32768, 64
 FAMILIES = ('cls', 'box_init', 'box_refine', 'kpt_init', 'kpt_refine')                 # the order of kgdet_serial_maps
 NAMES = ('loss_cls', 'loss_bbox_init', 'loss_bbox_refine', 'loss_kpt_init', 'loss_kpt_refine')
 
@@ -68,104 +70,62 @@ def applicable(head, cfg, cls_scores, keypts_preds_init, keypts_preds_refine, re
     """the fused kernels cover exactly: float32 CUDA maps outside autocast; focal + four smooth-L1 losses with 'mean';
     PointAssigner with a fixed pos_num for the init stage; MaxIoUAssigner with gt_max_assign_all and without ignore regions
     for the refine stage; consecutive power-of-two strides; ground truth on the maps' device within the header's limits"""
+    return why_not(head, cfg, cls_scores, keypts_preds_init, keypts_preds_refine, reppts_preds_init, reppts_preds_refine,
+                   gt_bboxes, gt_labels, gt_keypoints, img_metas, gt_bboxes_ignore) is None
+
+
+def why_not(head, cfg, cls_scores, keypts_preds_init, keypts_preds_refine, reppts_preds_init, reppts_preds_refine,
+            gt_bboxes, gt_labels, gt_keypoints, img_metas, gt_bboxes_ignore=None):
+    """None when ``applicable``, else the reason in words"""
     from .losses import FocalLoss, SmoothL1Loss
-    if not ENABLED or head.sampling or not head.use_sigmoid_cls:
-        return False
+    if not ENABLED:
+        return 'the fused serial loss is switched off (KGDET_FUSED_SERIAL_LOSS=0)'
+    if head.sampling or not head.use_sigmoid_cls:
+        return 'the head samples or has a softmax classifier'
     if type(head.loss_cls) is not FocalLoss or head.loss_cls.reduction != 'mean':
-        return False
+        return 'loss_cls is not FocalLoss with reduction "mean"'
     for n in NAMES[1:]:
         m = getattr(head, n)
         if type(m) is not SmoothL1Loss or m.reduction != 'mean' or not m.beta > 0:
-            return False
+            return '%s is not SmoothL1Loss with reduction "mean" and a positive beta' % n
     if not (gt_bboxes_ignore is None or all(g is None for g in gt_bboxes_ignore)):
-        return False
+        return 'the batch carries gt_bboxes_ignore'
     ai, ar = _assigners(cfg)
     if ai.get('type') != 'PointAssigner' or ai.get('pos_scale_factor') is not None:
-        return False
+        return 'the init assigner is no PointAssigner with a fixed pos_num'
     if ar.get('type') != 'MaxIoUAssigner' or not ar.get('gt_max_assign_all', True) or not ar.get('ignore_iof_thr', -1) < 0:
-        return False
+        return 'the refine assigner is no MaxIoUAssigner with gt_max_assign_all and without ignore regions'
     neg = ar.get('neg_iou_thr')
     if not (isinstance(neg, float) or (isinstance(neg, (tuple, list)) and len(neg) == 2)):
-        return False
+        return 'neg_iou_thr is neither a float nor a pair'
     strides = list(head.point_strides)
     L = len(strides)
     if not 1 <= L <= MAX_LEVELS or len(cls_scores) != L:
-        return False
+        return 'not 1..%d pyramid levels, one map each' % MAX_LEVELS
     first = strides[0]
     if first < 1 or int(first) != first or int(first) & (int(first) - 1) or \
             any(strides[l] != 2 * strides[l - 1] for l in range(1, L)):
-        return False
+        return 'the strides are not consecutive powers of two'
     t0 = cls_scores[0]
     B = t0.shape[0]
     if not t0.is_cuda or B > MAX_IMAGES or torch.is_autocast_enabled():
-        return False
+        return 'maps off the GPU, more than %d images, or autocast' % MAX_IMAGES
     for group in (cls_scores, keypts_preds_init, keypts_preds_refine, reppts_preds_init, reppts_preds_refine):
         if len(group) != L or any(m.dtype != torch.float32 or m.device != t0.device for m in group):
-            return False
+            return 'a family without one float32 map per level on one device'
     sizes = [tuple(m.shape[-2:]) for m in cls_scores]
     if any(h * w > MAX_LEVEL_POINTS for h, w in sizes):
-        return False
+        return 'a level of more than %d points' % MAX_LEVEL_POINTS
     pos_num = ai.get('pos_num', 3)
-    if not 1 <= pos_num <= MAX_POS_NUM or any(vh * vw < pos_num for per in valid_sizes(head, img_metas, sizes) for vh, vw in per):
-        return False
+    if not 1 <= pos_num <= MAX_POS_NUM:
+        return 'pos_num %d outside 1..%d' % (pos_num, MAX_POS_NUM)
+    if any(vh * vw < pos_num for per in valid_sizes(head, img_metas, sizes) for vh, vw in per):
+        return 'an image with fewer valid points than pos_num on some level'
     if len(gt_bboxes) != B:
-        return False
-    for b in range(B):
-        g = gt_bboxes[b].shape[0]
-        if g < 1 or g > MAX_GT or gt_bboxes[b].dtype != torch.float32 or gt_keypoints[b].dtype != torch.float32 or \
-                tuple(gt_keypoints[b].shape) != (g, head.num_keypts, 3):
-            return False
-        # the kernels dereference the raw ground-truth pointers: they must live on the maps' device
-        if gt_bboxes[b].device != t0.device or gt_keypoints[b].device != t0.device:
-            return False
-        if gt_labels is not None and gt_labels[b] is not None and (gt_labels[b].dtype != torch.int64 or
-                                                                   gt_labels[b].device != t0.device):
-            return False
-    return True
-
-
-class _SerialLoss(torch.autograd.Function):
-    """(cls, box_init, box_refine, kpt_init, kpt_refine maps of L levels) -> 5 x L 0-dim losses, family-major"""
-
-    @staticmethod
-    def forward(ctx, targets, cfg, keep, *maps):
-        L = _lib.lib()
-        maps = tuple(m.contiguous() for m in maps)
-        dev = maps[0].device
-        nl = targets.L
-        ws_bytes = L.kgdet_serial_loss_workspace_bytes(ctypes.byref(targets), ctypes.byref(cfg))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
-        out = torch.empty(5 * nl + 2, dtype=torch.float32, device=dev)       # the losses, then num_total init / refine
-        hm = _maps(maps, nl)
-        _lib.check(L.kgdet_serial_loss_forward(ctypes.byref(targets), ctypes.byref(cfg), ctypes.byref(hm), _lib.ptr(out),
-                                               ctypes.c_void_p(out.data_ptr() + 20 * nl), _lib.ptr(ws), ctypes.c_size_t(ws_bytes),
-                                               _lib.current_stream()), 'kgdet_serial_loss_forward')
-        ctx.targets, ctx.cfg, ctx.keep, ctx.ws, ctx.ws_bytes, ctx.out = targets, cfg, keep, ws, ws_bytes, out
-        ctx.save_for_backward(*maps)
-        return tuple(out[k] for k in range(5 * nl))
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grad_losses):
-        maps = ctx.saved_tensors
-        dev = maps[0].device
-        nl = ctx.targets.L
-        zero = None
-        gl = []
-        for g in grad_losses:
-            if g is None:
-                if zero is None:
-                    zero = torch.zeros((), dtype=torch.float32, device=dev)
-                g = zero
-            gl.append(g.reshape(()).float())
-        up = torch.stack(gl)
-        grads = tuple(torch.empty_like(m) for m in maps)
-        hm, hg = _maps(maps, nl), _maps(grads, nl)
-        _lib.check(_lib.lib().kgdet_serial_loss_backward(
-            ctypes.byref(ctx.targets), ctypes.byref(ctx.cfg), ctypes.byref(hm), _lib.ptr(up),
-            ctypes.c_void_p(ctx.out.data_ptr() + 20 * nl), ctypes.byref(hg), _lib.ptr(ctx.ws), ctypes.c_size_t(ctx.ws_bytes),
-            _lib.current_stream()), 'kgdet_serial_loss_backward')
-        return (None, None, None) + grads
+        return 'not one ground-truth tensor per image'
+    if any(k.shape[0] != g.shape[0] for g, k in zip(gt_bboxes, gt_keypoints)):
+        return 'an image whose keypoints and boxes differ in number'
+    return gt_why_not(B, t0.device, head.num_keypts, gt_bboxes, gt_labels, gt_keypoints)
 
 
 def descriptors(head, cfg, featmap_sizes, sizes_valid, gt_bboxes, gt_labels, gt_keypoints):
@@ -175,16 +135,8 @@ def descriptors(head, cfg, featmap_sizes, sizes_valid, gt_bboxes, gt_labels, gt_
     t.B, t.L, t.num_classes, t.num_keypoints = B, L, head.cls_out_channels, head.num_keypts
     for l, (h, w) in enumerate(featmap_sizes):
         t.H[l], t.W[l], t.stride[l] = int(h), int(w), float(head.point_strides[l])
-    keep = []
+    keep = fill_ground_truth(t, gt_bboxes, gt_labels, gt_keypoints)
     for b in range(B):
-        bb, kp = gt_bboxes[b].contiguous(), gt_keypoints[b].contiguous()
-        if bb.shape[0] == 0:
-            raise ValueError('No gt or bboxes')
-        lab = None if gt_labels is None or gt_labels[b] is None else gt_labels[b].contiguous()
-        keep += [bb, kp, lab]
-        t.num_gt[b] = bb.shape[0]
-        t.gt_bboxes[b], t.gt_keypoints[b] = bb.data_ptr(), kp.data_ptr()
-        t.gt_labels[b] = lab.data_ptr() if lab is not None else None
         for l in range(L):
             t.valid_h[b][l], t.valid_w[b][l] = int(sizes_valid[b][l][0]), int(sizes_valid[b][l][1])
     ai, ar = _assigners(cfg)
@@ -218,5 +170,8 @@ def serial_loss(head, cfg, *args):
     """The five loss lists of ``head.loss`` (one 0-dim tensor per level, as the reference returns); arguments as ``inputs``."""
     t, c, keep, maps = inputs(head, cfg, *args)
     L = t.L
-    out = _SerialLoss.apply(t, c, keep, *maps)
+    lib = _lib.lib()
+    out = FusedLoss.apply(bind(lib.kgdet_serial_loss_forward, t, c), bind(lib.kgdet_serial_loss_backward, t, c),
+                          lib.kgdet_serial_loss_workspace_bytes(ctypes.byref(t), ctypes.byref(c)), 5 * L,
+                          lambda tensors: _maps(tensors, L), keep, *maps)
     return {n: list(out[k * L:(k + 1) * L]) for k, n in enumerate(NAMES)}
