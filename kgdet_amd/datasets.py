@@ -110,6 +110,19 @@ def keypoint_transform(keypoints, img_shape, gt_labels, scale_factor, swap_pairs
     return np.stack(out, axis=0)
 
 
+def landmark_fields(dataset):
+    """the landmark tables every sample's ``img_meta`` and the flip refer to, set on ``dataset``"""
+    meta = landmark_meta()
+    dataset.gt_class_keypoints_dict = {c + 1: tuple(r) for c, r in enumerate(meta['landmark_ranges'])}
+    dataset.flip_pairs = meta['swap_pairs']
+    dataset.keypoint_groups = meta['groups']
+    perm = np.arange(294)
+    for pairs in dataset.flip_pairs:
+        for a, b in pairs:
+            perm[a], perm[b] = b, a
+    dataset.flip_indices = np.stack([perm * 2, perm * 2 + 1], axis=1).reshape(-1)   # over interleaved (x, y) channels
+
+
 @DATASETS.register_module
 class DeepFashion2Dataset(object):
     CLASSES = tuple(landmark_meta()['classes'])
@@ -121,15 +134,7 @@ class DeepFashion2Dataset(object):
                  skip_img_without_anno=True, test_mode=False, group_mode=False):
         if with_mask or with_semantic_seg or proposal_file is not None or corruption:
             raise NotImplementedError('masks / proposals / corruption are outside the KGDet path')
-        meta = landmark_meta()
-        self.gt_class_keypoints_dict = {c + 1: tuple(r) for c, r in enumerate(meta['landmark_ranges'])}
-        self.flip_pairs = meta['swap_pairs']
-        self.keypoint_groups = meta['groups']
-        perm = np.arange(294)
-        for pairs in self.flip_pairs:
-            for a, b in pairs:
-                perm[a], perm[b] = b, a
-        self.flip_indices = np.stack([perm * 2, perm * 2 + 1], axis=1).reshape(-1)   # over interleaved (x, y) channels
+        landmark_fields(self)
 
         self.img_prefix = img_prefix
         self.coco = CocoIndex(ann_file)
@@ -341,6 +346,27 @@ class DeepFashion2Dataset(object):
             if data is not None:
                 return data
             idx = int(np.random.choice(np.where(self.flag == self.flag[idx])[0]))
+
+
+def finish_train_sample(dataset, raw_sample):
+    """The pixel work ``prepare_train_img`` does after its draws, on a ``prepare_train_raw`` sample: ``img_transform`` -- or
+    ``image_transform_restatement_aug`` where the sample carries an ``aug_plan`` -- on ``raw`` with the drawn ``scale`` and
+    ``flip``; returns the dict ``prepare_train_img`` returns (same keys, same order, same bits).  It draws nothing, so it may
+    run on any thread (``kgdet_amd.loader`` runs it in its pool, behind the one thread that makes the draws)."""
+    raw, aug = raw_sample['raw'].numpy(), raw_sample.get('aug_plan')
+    scale, flip, keep_ratio = raw_sample['scale'], raw_sample['flip'], raw_sample['keep_ratio']
+    if aug is None:
+        img, img_shape, pad_shape, sf = dataset.img_transform(raw, scale, flip, keep_ratio=keep_ratio)
+    else:
+        from .preprocess import image_transform_restatement_aug
+        img, img_shape, pad_shape, sf = image_transform_restatement_aug(
+            raw, aug, scale, flip, keep_ratio, size_divisor=dataset.size_divisor, **dataset.img_norm_cfg)
+    meta = dict(raw_sample['img_meta'], img_shape=img_shape, pad_shape=pad_shape, scale_factor=sf)
+    data = dict(img=torch.from_numpy(img), img_meta=meta)
+    for key, value in raw_sample.items():
+        if key not in ('raw', 'scale', 'flip', 'keep_ratio', 'img_meta', 'aug_plan'):
+            data[key] = value
+    return data
 
 
 def collate(batch):

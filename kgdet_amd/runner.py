@@ -202,23 +202,63 @@ class _RowSink(object):
         self.put(model.simple_test_batch_device(img, metas, rescale=rescale))
 
 
-def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None):
+class _Prefetched(object):
+    """``fn(indices[k])`` for k = 0, 1, 2, ... as the test loops ask for them -- strictly in that order, each once --, computed in
+    a pool of ``workers`` threads (at most 16) a bounded window ahead (two samples per thread).  Test-time samples make no
+    random draws, so the whole preparation runs in the pool; an exception there is raised by the call that asks for its
+    sample, with its type."""
+
+    def __init__(self, fn, indices, workers):
+        from collections import deque
+        from concurrent.futures import ThreadPoolExecutor
+        workers = min(int(workers), 16)
+        self.fn, self.indices, self.window = fn, indices, 2 * workers
+        self.pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix='kgdet-test-prefetch')
+        self.futures, self.at, self.submitted = deque(), 0, 0
+
+    def __call__(self, k):
+        assert k == self.at, 'the test loops read their samples in order, each once'
+        while self.submitted < min(len(self.indices), k + 1 + self.window):
+            self.futures.append(self.pool.submit(self.fn, self.indices[self.submitted]))
+            self.submitted += 1
+        self.at += 1
+        return self.futures.popleft().result()
+
+    def close(self):
+        self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None, workers=0):
     """results of the samples ``indices`` in that order.  imgs_per_gpu == 1: the reference's call, one image per forward
     (``model(return_loss=False, rescale=..., **data)``, tools/test.py:25-28); > 1: runs of consecutive samples with identical
     tensor shapes and one augmentation go through ``simple_test_batch`` together (the same per-image results: nothing in
     backbone / neck / head / decode / NMS mixes the images of a batch).  ``device_preprocess``: the input transform runs on the
-    model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then)."""
+    model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then).  ``workers`` > 0: the samples are
+    prepared ahead in that many threads (``_Prefetched``) and consumed in the same order -- the same calls, the same results."""
+    if workers < 0:
+        raise ValueError('workers is >= 0, got %r' % (workers,))
+    if workers:
+        fn = dataset.prepare_test_raw if device_preprocess else dataset.__getitem__
+        ahead = _Prefetched(fn, indices, workers)
+        try:
+            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead)
+        finally:
+            ahead.close()
+    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None)
+
+
+def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead):
     if device_preprocess:
-        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink)
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
     while i < len(indices):
-        data = carried if carried is not None else dataset[indices[i]]
+        data = carried if carried is not None else (dataset[indices[i]] if ahead is None else ahead(i))
         carried = None
         group = [data]
         while (imgs_per_gpu > 1 and len(group) < imgs_per_gpu and i + len(group) < len(indices) and len(data['img']) == 1):
-            nxt = dataset[indices[i + len(group)]]
+            nxt = dataset[indices[i + len(group)]] if ahead is None else ahead(i + len(group))
             if len(nxt['img']) != 1 or nxt['img'][0].shape != data['img'][0].shape:
                 carried = nxt
                 break
@@ -245,7 +285,7 @@ def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device
     return results
 
 
-def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None):
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None):
     """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
     planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
     ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
@@ -255,12 +295,12 @@ def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None)
     results, i = [], 0
     carried = None
     while i < len(indices):
-        data = carried if carried is not None else dataset.prepare_test_raw(indices[i])
+        data = carried if carried is not None else (dataset.prepare_test_raw(indices[i]) if ahead is None else ahead(i))
         carried = None
         group = [data]
         while (imgs_per_gpu > 1 and len(group) < imgs_per_gpu and i + len(group) < len(indices)
                and len(data['img_meta']) == 1):
-            nxt = dataset.prepare_test_raw(indices[i + len(group)])
+            nxt = dataset.prepare_test_raw(indices[i + len(group)]) if ahead is None else ahead(i + len(group))
             if len(nxt['img_meta']) != 1 or nxt['img_meta'][0]['pad_shape'] != data['img_meta'][0]['pad_shape']:
                 carried = nxt
                 break
@@ -285,21 +325,23 @@ def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None)
 
 
 def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False,
-                    device_results=False):
+                    device_results=False, workers=0):
     """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
     resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
     used then) instead of ``dataset[i]``'s host transform; same result format and order.  ``device_results``: the
     detections stay on the device -- a ``DeviceResults`` comes back instead of the list (its ``to_host()`` IS that list): no
     download and no per-class split per batch.  ``NotImplementedError`` for ``test_cfg.max_per_img <= 0`` (before the run) or
-    an image with more detections than that."""
+    an image with more detections than that.  ``workers``: threads that decode and prepare the upcoming samples (``_test_on``);
+    0 prepares each sample inline, as the reference's loop does."""
     if not device_results:
-        return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess)
+        return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess,
+                        workers=workers)
     target = model.module if hasattr(model, 'module') else model
     M = int(target.test_cfg.max_per_img)
     if M <= 0:
         raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
     sink = _RowSink(len(dataset))
-    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink)
+    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink, workers)
     rows = sink.rows
     if rows is None:                            # (an empty dataset)
         rows = torch.empty((0, M, 10), dtype=torch.float32, device=next(target.parameters()).device)
@@ -328,15 +370,16 @@ def collect_results(result_part, size, group=None):
     return ordered[:size]
 
 
-def multi_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, group=None, device_preprocess=False):
+def multi_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, group=None, device_preprocess=False,
+                   workers=0):
     """tools/test.py:38-58: every rank runs its shard of the dataset, rank 0 returns all results in dataset order
-    (``device_preprocess``: as in ``single_gpu_test``, on each rank's own device)"""
+    (``device_preprocess`` and ``workers``: as in ``single_gpu_test``, on each rank's own device)"""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if on else 1
     rank = dist.get_rank(group) if on else 0
     part = _test_on(model, dataset, test_shard(len(dataset), world, rank), rescale, to_device, imgs_per_gpu,
-                    device_preprocess)
+                    device_preprocess, workers=workers)
     return collect_results(part, len(dataset), group)
 
 
@@ -503,12 +546,14 @@ class GraphedTrainStep(object):
 
 class Runner(object):
     def __init__(self, model, optimizer, work_dir=None, lr_config=None, optimizer_config=None, checkpoint_config=None,
-                 log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None):
+                 log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None, on_record=None):
         """``eval_config = dict(dataset=..., interval=1, imgs_per_gpu=1, device_preprocess=False, group=None, to_device=None,
-        result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None, device_results=False)``:
+        result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None, device_results=False,
+        workers=0)``:
         validation after every ``interval``-th epoch (``validate``); ``lazy_landmarks`` and ``device_accumulate`` are
-        ``evaluation_device.evaluate_results``'s, ``device_results`` is ``single_gpu_test``'s (with ``group`` it is refused:
-        ``multi_gpu_test`` gathers host lists)."""
+        ``evaluation_device.evaluate_results``'s, ``device_results`` and ``workers`` are ``single_gpu_test``'s (``device_results``
+        with ``group`` is refused: ``multi_gpu_test`` gathers host lists).  ``on_record(mode, record)``: called with 'train' or
+        'val' and every record as it is appended to ``log_history`` (``apis.train_detector`` writes its ``.log.json`` there)."""
         self.model, self.optimizer, self.work_dir = model, optimizer, work_dir
         self.eval_config = dict(eval_config) if eval_config else None
         if self.eval_config and self.eval_config.get('device_results') and self.eval_config.get('group') is not None:
@@ -519,7 +564,7 @@ class Runner(object):
         self.ckpt_interval = (checkpoint_config or {}).get('interval', 1)
         self.log_interval, self.logger, self.batch_processor = log_interval, logger, batch_processor
         self.epoch, self.iter = 0, 0
-        self.log_history = []
+        self.log_history, self.on_record = [], on_record
         self.graphed = None      # a GraphedTrainStep driven by the caller (`attach_graphed`): re-captured when a layer is rerouted
 
     def attach_graphed(self, step):
@@ -550,6 +595,11 @@ class Runner(object):
             self.logger('envelope: %d layer(s) rerouted to bf16 parts, the graphed step was captured again' % len(rerouted))
         return rerouted
 
+    def _record(self, mode, rec):
+        self.log_history.append(rec)
+        if self.on_record is not None:
+            self.on_record(mode, rec)
+
     def current_lr(self):
         return [g['lr'] for g in self.optimizer.param_groups]
 
@@ -572,11 +622,22 @@ class Runner(object):
         """``to_device(data)`` turns what the loader yields into the batch dict on the GPU.  For the device-side input
         transform let the loader yield lists of ``dataset.prepare_train_raw`` samples and pass
         ``to_device=lambda samples: move(datasets.collate_device(samples, dataset.device_transform()))`` with ``move``
-        the usual host->device copy of the ground-truth lists (the image is made on the GPU by one launch)."""
+        the usual host->device copy of the ground-truth lists (the image is made on the GPU by one launch) -- or hand in a
+        ``loader.build_dataloader(..., device=...)``, whose batches are on the GPU already (``to_device=None``).  Each log record
+        carries ``data_time`` beside ``time``: the mean seconds per iteration spent waiting in the loader's ``next()`` (mmcv's field
+        of that name) -- the number that says whether the feed keeps up."""
         self.model.train()
         self.lr.before_train_epoch(self.optimizer, self.epoch)
-        t0 = time.time()
-        for i, data in enumerate(data_loader):
+        t0, waited = time.time(), 0.0
+        batches, i = iter(data_loader), -1
+        while True:
+            t_next = time.time()
+            try:
+                data = next(batches)
+            except StopIteration:
+                break
+            waited += time.time() - t_next
+            i += 1
             self.lr.before_train_iter(self.optimizer, self.iter)
             if to_device is not None:
                 data = to_device(data)
@@ -585,9 +646,9 @@ class Runner(object):
             self.iter += 1
             if self.log_interval and (i + 1) % self.log_interval == 0:
                 rec = OrderedDict(epoch=self.epoch + 1, iter=i + 1, lr=self.current_lr()[0],
-                                  time=(time.time() - t0) / (i + 1))
+                                  time=(time.time() - t0) / (i + 1), data_time=waited / (i + 1))
                 rec.update((k, float(v.detach()) if isinstance(v, torch.Tensor) else float(v)) for k, v in out['log_vars'].items())     # the only device->host read
-                self.log_history.append(rec)
+                self._record('train', rec)
                 self.logger(', '.join('%s: %.5g' % kv if isinstance(kv[1], float) else '%s: %s' % kv for kv in rec.items()))
         self.epoch += 1
 
@@ -622,7 +683,7 @@ class Runner(object):
         self.model.eval()
         try:
             kw = dict(rescale=True, to_device=cfg.get('to_device'), imgs_per_gpu=cfg.get('imgs_per_gpu', 1),
-                      device_preprocess=cfg.get('device_preprocess', False))
+                      device_preprocess=cfg.get('device_preprocess', False), workers=cfg.get('workers', 0))
             if group is not None:
                 results = multi_gpu_test(self.model, dataset, group=group, **kw)
             else:
@@ -646,6 +707,6 @@ class Runner(object):
             for i, name in enumerate(names):
                 rec['{}_{}'.format(t, name)] = float('{:.3f}'.format(stats[t][i]))
             rec['{}_mAP_copypaste'.format(t)] = ('{:.3f} ' * 6).format(*stats[t][:6]).strip()
-        self.log_history.append(rec)
+        self._record('val', rec)
         self.logger(', '.join('%s: %s' % kv for kv in rec.items()))
         return rec

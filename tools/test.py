@@ -1,0 +1,72 @@
+"""Test a detector from a config file and a checkpoint (the reference's ``tools/test.py``), one process on one GPU.
+
+    python tools/test.py CONFIG CHECKPOINT [--json_out P] [--eval bbox keypoints] [--workers N] [--imgs-per-gpu N]
+                                           [--device-preprocess] [--device-results]
+
+``cfg.data.test`` goes through ``runner.single_gpu_test``: ``--workers`` threads decode and prepare the upcoming images
+(default ``cfg.data.workers_per_gpu``), ``--imgs-per-gpu`` images of one shape share a forward pass, ``--device-preprocess``
+runs the input transform on the GPU, ``--device-results`` keeps the detections in device memory until they are evaluated.
+``--json_out P`` writes ``P.bbox.json`` / ``P.keypoints.json`` through ``evaluation.results2json`` and evaluates those files
+with ``coco_eval``; without it ``--eval`` evaluates the results where they lie (``evaluation_device.evaluate_results``).  A
+``--launcher`` other than ``none`` is refused: the multi-rank launch is not part of this tool."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser(description='Test a detector')
+    parser.add_argument('config', help='test config file path')
+    parser.add_argument('checkpoint', help='checkpoint file')
+    parser.add_argument('--json_out', help='output result file name without extension')
+    parser.add_argument('--eval', nargs='+', choices=['bbox', 'keypoints'], help='eval types')
+    parser.add_argument('--workers', type=int, default=None, help='threads that prepare upcoming images')
+    parser.add_argument('--imgs-per-gpu', type=int, default=1)
+    parser.add_argument('--device-preprocess', action='store_true')
+    parser.add_argument('--device-results', action='store_true')
+    parser.add_argument('--launcher', default='none', help='job launcher (only "none")')
+    return parser.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    if args.launcher != 'none':
+        raise SystemExit('--launcher %s: this tool runs one process on one GPU (the multi-rank launch is a separate tool)'
+                         % args.launcher)
+    if not (args.json_out or args.eval):
+        raise SystemExit('nothing to do: give --json_out and / or --eval')
+    import torch
+    from kgdet_amd import Config, evaluation, evaluation_device
+    from kgdet_amd.apis import init_detector
+    from kgdet_amd.datasets import build_dataset
+    from kgdet_amd.runner import single_gpu_test
+    if not torch.cuda.is_available():
+        raise SystemExit('tools/test.py needs a GPU')
+    cfg = Config.fromfile(args.config)
+    cfg.data.test.test_mode = True
+    dataset = build_dataset(cfg.data.test)
+    model = init_detector(cfg, args.checkpoint, device='cuda:0')
+    workers = cfg.data.get('workers_per_gpu', 0) if args.workers is None else args.workers
+    results = single_gpu_test(model, dataset, rescale=True, to_device=lambda t: t.cuda(non_blocking=True),
+                              imgs_per_gpu=args.imgs_per_gpu, device_preprocess=args.device_preprocess,
+                              device_results=args.device_results, workers=min(workers, 16))
+    stats = None
+    if args.json_out:
+        out = args.json_out[:-5] if args.json_out.endswith('.json') else args.json_out
+        host = results.to_host() if args.device_results else results
+        print('writing results to {}'.format(out))
+        files = evaluation.results2json(dataset, host, out)
+        if args.eval:
+            print('Starting evaluate {}'.format(' and '.join(args.eval)))
+            stats = evaluation.coco_eval(files, args.eval, dataset.coco, device='cuda:0')
+    elif args.eval:
+        print('Starting evaluate {}'.format(' and '.join(args.eval)))
+        stats = evaluation_device.evaluate_results(dataset, results, args.eval, device='cuda:0', verbose=True)
+    return stats
+
+
+if __name__ == '__main__':
+    main()
