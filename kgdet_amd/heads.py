@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import conv1x1, dcn, moment
+from . import conv1x1, dcn, decode, moment
 from .layers import ConvModule, bias_init_with_prob, normal_init
 from .points import (PointGenerator, dense_targets_applicable, multi_apply, point_target_kp,
                      point_target_kp_dense)
@@ -293,6 +293,30 @@ class PointHeadMixin(object):
             pts_list.append(pts.reshape(B, -1, 2 * num_points))
         return pts_list
 
+    # ---- after the decode (decode.py), the same for every head ---------------------------------
+    def candidates_to_results(self, bboxes, scores, kpts, cfg, nms, batched_hard_nms=False):
+        """decoded candidates of a batch -> per image (det [n, 5], labels [n], landmarks) after NMS; for ``nms=False`` the
+        candidates themselves, (bboxes [n, 4], scores [n, 1 + C], landmarks), as test-time augmentation merges them"""
+        if self.use_sigmoid_cls:        # the background column the NMS skips
+            scores = torch.cat([scores.new_zeros(scores.shape[:2] + (1, )), scores], dim=2)
+        if not nms:
+            return [(bboxes[b], scores[b], kpts[b]) for b in range(bboxes.shape[0])]
+        if batched_hard_nms and cfg.nms.get('type', 'nms') == 'nms':
+            return multiclass_nms_kp_batched(bboxes, scores, kpts, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        return [multiclass_nms_kp(bboxes[b], scores[b], kpts[b], cfg.score_thr, cfg.nms, cfg.max_per_img)
+                for b in range(bboxes.shape[0])]
+
+    unpack_results = staticmethod(decode.unpack_results)
+
+    def get_bboxes_numpy(self, *args, **kwargs):
+        """``get_bboxes`` with the results on the host as numpy arrays; on the packed path the whole batch comes
+        back in ONE device->host copy."""
+        packed = self.get_bboxes_packed_tensor(*args, **kwargs)
+        if packed is None:
+            return [(d.float().cpu().numpy(), lab.cpu().numpy(), k.float().flatten(1).cpu().numpy())
+                    for d, lab, k in self.get_bboxes(*args, **kwargs)]
+        return self.unpack_results(packed.cpu().numpy())
+
 
 @HEADS.register_module
 class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
@@ -525,140 +549,7 @@ class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
         return dict(zip(names, per_level))
 
     # ------------------------------------------------------------------------------------------
-    def _decode_level(self, cls_score, bbox_pred, kpt_pred, points, stride, img_shape, cfg):
-        """one image, one level: scores [n, C], boxes [n, 4], keypoints [n, K, 3] in image coordinates"""
-        num_kpt = self.num_keypts
-        num_kp_channel = kpt_pred.size(0) // num_kpt
-        assert num_kp_channel == 2 or num_kp_channel == 3
-        assert cls_score.size()[-2:] == bbox_pred.size()[-2:] == kpt_pred.size()[-2:]
-        cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
-        scores = cls_score.sigmoid() if self.use_sigmoid_cls else cls_score.softmax(-1)
-        bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
-        if num_kp_channel == 3:
-            kpt_pred = kpt_pred.permute(1, 2, 0).reshape(-1, num_kpt * num_kp_channel)
-        else:  # visibility not predicted: pad with 1
-            kpt_pred = kpt_pred.permute(1, 2, 0).reshape(-1, num_kpt, num_kp_channel)
-            kpt_pred = torch.cat([kpt_pred, kpt_pred.new_full(kpt_pred[:, :, :1].size(), 1)], dim=2)
-            kpt_pred = kpt_pred.reshape(-1, num_kpt * 3)
-        nms_pre = cfg.get('nms_pre', -1)
-        if nms_pre > 0 and scores.shape[0] > nms_pre:
-            max_scores, _ = scores.max(dim=1) if self.use_sigmoid_cls else scores[:, 1:].max(dim=1)
-            _, topk_inds = max_scores.topk(nms_pre)
-            points = points[topk_inds, :]
-            bbox_pred = bbox_pred[topk_inds, :]
-            kpt_pred = kpt_pred[topk_inds, :]
-            scores = scores[topk_inds, :]
-        bbox_pos_center = torch.cat([points[:, :2], points[:, :2]], dim=1)
-        bboxes = bbox_pred * stride + bbox_pos_center
-        kpts = kpt_pred.view(-1, num_kpt, 3).clone()
-        kpts[:, :, :2] = kpts[:, :, :2] * stride + points[:, :2].unsqueeze(dim=1)
-        # clamp to img_shape itself, not img_shape - 1 (KP3:882-888)
-        bboxes = torch.stack([bboxes[:, 0].clamp(min=0, max=img_shape[1]), bboxes[:, 1].clamp(min=0, max=img_shape[0]),
-                              bboxes[:, 2].clamp(min=0, max=img_shape[1]), bboxes[:, 3].clamp(min=0, max=img_shape[0])],
-                             dim=-1)
-        kpts[:, :, 0] = kpts[:, :, 0].clamp(min=0, max=img_shape[1])
-        kpts[:, :, 1] = kpts[:, :, 1].clamp(min=0, max=img_shape[0])
-        return bboxes, scores, kpts
-
-    def get_bboxes_single(self, cls_scores, bbox_preds, kpt_preds, mlvl_points, img_shape, scale_factor, cfg,
-                          rescale=False, nms=True):
-        assert len(cls_scores) == len(bbox_preds) == len(mlvl_points) == len(kpt_preds)
-        decoded = [self._decode_level(c, b, k, p, self.point_strides[i], img_shape, cfg)
-                   for i, (c, b, k, p) in enumerate(zip(cls_scores, bbox_preds, kpt_preds, mlvl_points))]
-        mlvl_bboxes = torch.cat([d[0] for d in decoded])
-        mlvl_scores = torch.cat([d[1] for d in decoded])
-        mlvl_kpts = torch.cat([d[2] for d in decoded])
-        if rescale:
-            # (a scalar factor divides directly; new_tensor() is a blocking host->device upload per image)
-            sf = scale_factor if isinstance(scale_factor, (int, float)) else mlvl_bboxes.new_tensor(scale_factor)
-            mlvl_bboxes /= sf
-            mlvl_kpts[:, :, 0:2] = mlvl_kpts[:, :, 0:2] / sf
-            mlvl_kpts = mlvl_kpts.reshape(-1, self.num_keypts * 3)
-        if self.use_sigmoid_cls:
-            padding = mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)
-            mlvl_scores = torch.cat([padding, mlvl_scores], dim=1)
-        if nms:
-            return multiclass_nms_kp(mlvl_bboxes, mlvl_scores, mlvl_kpts, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        return mlvl_bboxes, mlvl_scores, mlvl_kpts
-
-    def get_bboxes(self, cls_scores_1, cls_scores_2, cls_scores_3, keypts_preds_1, keypts_preds_2, keypts_preds_3,
-                   bbox_preds_1, bbox_preds_2, bbox_preds_3, img_metas, cfg, rescale=False, nms=True):
-        """detections from the final stage.  With hard NMS the whole batch is suppressed in one launch."""
-        # decode in fp32 whatever the convolutions ran in: bf16 cannot hold a pixel coordinate (8-bit mantissa)
-        cls_score_final = [t.float() for t in cls_scores_3]
-        bbox_preds = [t.float() for t in bbox_preds_3]
-        keypts_preds_final = [t.float() for t in keypts_preds_3]
-        assert len(cls_score_final) == len(keypts_preds_final) == len(bbox_preds)
-        kpt_preds = [self.points2kpt(keypts_pred) for keypts_pred in keypts_preds_final]
-        num_levels = len(cls_score_final)
-        device = cls_score_final[0].device
-        mlvl_points = [
-            self.point_generators[i].grid_points(cls_score_final[i].size()[-2:], self.point_strides[i], device=device)
-            for i in range(num_levels)
-        ]
-        if nms and self._packed_ok(cls_score_final, img_metas, cfg):
-            det, label, kp, count = self.get_bboxes_packed(cls_score_final, bbox_preds, kpt_preds, mlvl_points,
-                                                           img_metas, cfg, rescale)
-            counts = count.tolist()                      # the only device->host read of the post-processing
-            return [(det[b, :n], label[b, :n], kp[b, :n]) for b, n in enumerate(counts)]
-        per_image = []
-        for img_id in range(len(img_metas)):
-            cls_score_list = [cls_score_final[i][img_id].detach() for i in range(num_levels)]
-            bbox_pred_list = [bbox_preds[i][img_id].detach() for i in range(num_levels)]
-            kpt_pred_list = [kpt_preds[i][img_id].detach() for i in range(num_levels)]
-            img_shape = img_metas[img_id]['img_shape']
-            scale_factor = img_metas[img_id]['scale_factor']
-            batched = nms and cfg.nms.get('type', 'nms') == 'nms' and cls_score_final[0].is_cuda
-            per_image.append(self.get_bboxes_single(cls_score_list, bbox_pred_list, kpt_pred_list, mlvl_points,
-                                                    img_shape, scale_factor, cfg, rescale, nms and not batched))
-        if not (nms and cfg.nms.get('type', 'nms') == 'nms' and cls_score_final[0].is_cuda):
-            return per_image
-        n_max = max(p[0].shape[0] for p in per_image)
-
-        def pad(t):
-            return t if t.shape[0] == n_max else torch.cat([t, t.new_zeros((n_max - t.shape[0], ) + t.shape[1:])])
-
-        return multiclass_nms_kp_batched(torch.stack([pad(p[0]) for p in per_image]),
-                                         torch.stack([pad(p[1]) for p in per_image]),
-                                         torch.stack([pad(p[2]) for p in per_image]), cfg.score_thr, cfg.nms,
-                                         cfg.max_per_img)
-
-    def get_bboxes_packed_tensor(self, cls_scores_1, cls_scores_2, cls_scores_3, keypts_preds_1, keypts_preds_2,
-                                 keypts_preds_3, bbox_preds_1, bbox_preds_2, bbox_preds_3, img_metas, cfg,
-                                 rescale=False):
-        """The batch's detections as ONE device tensor [B, max_per_img, 7 + 3K] -- columns: box (4), score, label,
-        count (repeated), landmarks -- produced without any host read (capturable in a HIP graph); None when the
-        packed path does not apply.  ``unpack_results`` splits its host copy per image."""
-        cls3, box3 = [t.float() for t in cls_scores_3], [t.float() for t in bbox_preds_3]
-        if not self._packed_ok(cls3, img_metas, cfg):
-            return None
-        kpt3 = [self.points2kpt(t.float()) for t in keypts_preds_3]
-        points = [self.point_generators[i].grid_points(cls3[i].size()[-2:], self.point_strides[i], device=cls3[i].device)
-                  for i in range(len(cls3))]
-        det, label, kp, count = self.get_bboxes_packed(cls3, box3, kpt3, points, img_metas, cfg, rescale)
-        B, M = label.shape
-        return torch.cat([det, label.unsqueeze(-1).float(), count.view(B, 1, 1).expand(B, M, 1).float(), kp], dim=-1)
-
-    @staticmethod
-    def unpack_results(packed):
-        """host copy of ``get_bboxes_packed_tensor`` -> per image (det [n, 5], labels [n] int64, landmarks [n, 3K])"""
-        out = []
-        for b in range(packed.shape[0]):
-            n = int(packed[b, 0, 6])
-            out.append((packed[b, :n, :5], packed[b, :n, 5].astype(np.int64), packed[b, :n, 7:]))
-        return out
-
-    def get_bboxes_numpy(self, *args, **kwargs):
-        """``get_bboxes`` with the results on the host as numpy arrays; on the packed path the whole batch comes
-        back in ONE device->host copy."""
-        packed = self.get_bboxes_packed_tensor(*args, **kwargs)
-        if packed is None:
-            return [(d.float().cpu().numpy(), lab.cpu().numpy(), k.float().cpu().numpy())
-                    for d, lab, k in self.get_bboxes(*args, **kwargs)]
-        return self.unpack_results(packed.cpu().numpy())
-
-    # ------------------------------------------------------------------------------------------
-    # whole-batch decode + fused NMS: no per-image Python loop, no host read before the results
+    # detections from the final stage: one whole-batch decode (decode.py), then NMS
     # ------------------------------------------------------------------------------------------
     def _packed_ok(self, cls_scores, img_metas, cfg):
         if not (cls_scores[0].is_cuda and cfg.nms.get('type', 'nms') == 'nms' and self.use_sigmoid_cls
@@ -670,69 +561,43 @@ class RepPointsHeadKp3RepCas1AssignOnce(PointHeadMixin, nn.Module):
                 else c.shape[-2] * c.shape[-1] for c in cls_scores)
         return n <= 4096 and n * self.cls_out_channels <= 16384 and self.cls_out_channels <= 64
 
-    @staticmethod
-    def _per_image(values, device):
-        """python numbers, one per image -> a scalar when they agree, else a [B, 1] tensor uploaded without blocking"""
-        if all(v == values[0] for v in values):
-            return values[0]
-        return torch.tensor(values, dtype=torch.float32).pin_memory().to(device, non_blocking=True).unsqueeze(1)
+    def _decode(self, cls_scores, bbox_preds, keypts_preds, img_metas, cfg, rescale):
+        """final-stage maps -> boxes [B, M, 4], scores [B, M, C], landmarks of the whole batch.  Decoded in fp32 whatever the
+        convolutions ran in: bf16 cannot hold a pixel coordinate (8-bit mantissa)"""
+        kpt_preds = [self.points2kpt(t.detach().float()) for t in keypts_preds]
+        return decode.decode_batch(self, cls_scores, [t.detach().float() for t in bbox_preds], kpt_preds, img_metas, cfg,
+                                   rescale, clamp_axis='coordinate', true_divide=False)
 
-    def _decode_level_batch(self, cls_score, bbox_pred, kpt_pred, points, stride, lim_w, lim_h, cfg):
-        """``_decode_level`` for all images at once: scores [B,n,C], boxes [B,n,4], landmarks [B,n,K,3]"""
-        B, num_kpt = cls_score.shape[0], self.num_keypts
-        ch = kpt_pred.size(1) // num_kpt
-        assert ch == 2 or ch == 3
-        scores = cls_score.permute(0, 2, 3, 1).reshape(B, -1, self.cls_out_channels).sigmoid()
-        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(B, -1, 4)
-        kpt_pred = kpt_pred.permute(0, 2, 3, 1).reshape(B, -1, num_kpt, ch)
-        if ch == 2:
-            kpt_pred = torch.cat([kpt_pred, kpt_pred.new_ones(kpt_pred[..., :1].shape)], dim=-1)
-        ctr = points[:, :2].unsqueeze(0).expand(B, -1, -1)
-        nms_pre = cfg.get('nms_pre', -1)
-        if nms_pre > 0 and scores.shape[1] > nms_pre:
-            _, top = scores.max(dim=2)[0].topk(nms_pre, dim=1)
-            ctr = torch.gather(ctr, 1, top.unsqueeze(-1).expand(B, nms_pre, 2))
-            bbox_pred = torch.gather(bbox_pred, 1, top.unsqueeze(-1).expand(B, nms_pre, 4))
-            kpt_pred = torch.gather(kpt_pred, 1, top.view(B, nms_pre, 1, 1).expand(B, nms_pre, num_kpt, 3))
-            scores = torch.gather(scores, 1, top.unsqueeze(-1).expand(B, nms_pre, scores.shape[2]))
-        bboxes = bbox_pred * stride + torch.cat([ctr, ctr], dim=2)
-        kpts = kpt_pred.clone()
-        kpts[..., :2] = kpts[..., :2] * stride + ctr.unsqueeze(2)
-
-        def clamp(t, lim):      # to [0, img_shape] (not img_shape - 1, KP3:882-888)
-            if isinstance(lim, (int, float)):
-                return t.clamp(min=0, max=lim)
-            return torch.minimum(t.clamp(min=0), lim.view((B, ) + (1, ) * (t.dim() - 1)))
-
-        bboxes = torch.stack([clamp(bboxes[..., 0], lim_w), clamp(bboxes[..., 1], lim_h), clamp(bboxes[..., 2], lim_w),
-                              clamp(bboxes[..., 3], lim_h)], dim=-1)
-        kpts[..., 0] = clamp(kpts[..., 0], lim_w)
-        kpts[..., 1] = clamp(kpts[..., 1], lim_h)
-        return bboxes, scores, kpts
-
-    def get_bboxes_packed(self, cls_scores, bbox_preds, kpt_preds, mlvl_points, img_metas, cfg, rescale=False):
-        """final-stage maps -> fixed-size device tensors (det [B,M,5], labels [B,M], landmarks [B,M,3K], count [B])"""
-        device = cls_scores[0].device
-        lim_w = self._per_image([float(m['img_shape'][1]) for m in img_metas], device)
-        lim_h = self._per_image([float(m['img_shape'][0]) for m in img_metas], device)
-        decoded = [self._decode_level_batch(cls_scores[i].detach().float(), bbox_preds[i].detach().float(),
-                                            kpt_preds[i].detach().float(), mlvl_points[i], self.point_strides[i],
-                                            lim_w, lim_h, cfg) for i in range(len(cls_scores))]
-        bboxes = torch.cat([d[0] for d in decoded], dim=1)
-        scores = torch.cat([d[1] for d in decoded], dim=1)
-        kpts = torch.cat([d[2] for d in decoded], dim=1)
-        if rescale:
-            sf = self._per_image([float(m['scale_factor']) for m in img_metas], device)
-            if isinstance(sf, float):
-                bboxes = bboxes / sf
-                kpts[..., 0:2] = kpts[..., 0:2] / sf
-            else:   # torch divides by a python scalar as x * (1 / s) in fp32: do the same per image
-                inv = torch.reciprocal(sf)
-                bboxes = bboxes * inv.view(-1, 1, 1)
-                kpts[..., 0:2] = kpts[..., 0:2] * inv.view(-1, 1, 1, 1)
+    def get_bboxes_packed(self, cls_scores, bbox_preds, keypts_preds, img_metas, cfg, rescale=False):
+        """final-stage maps -> fixed-size device tensors (det [B,M,5], labels [B,M], landmarks [B,M,3K], count [B]): decode
+        and fused NMS of the whole batch with no host read before the results"""
         from .postprocess import multiclass_nms_kp_fused
+        bboxes, scores, kpts = self._decode(cls_scores, bbox_preds, keypts_preds, img_metas, cfg, rescale)
         return multiclass_nms_kp_fused(bboxes, scores, kpts.reshape(kpts.shape[0], kpts.shape[1], -1), cfg.score_thr,
                                        float(cfg.nms['iou_thr']), cfg.max_per_img)
+
+    def get_bboxes(self, cls_scores_1, cls_scores_2, cls_scores_3, keypts_preds_1, keypts_preds_2, keypts_preds_3,
+                   bbox_preds_1, bbox_preds_2, bbox_preds_3, img_metas, cfg, rescale=False, nms=True):
+        """detections from the final stage.  With hard NMS the whole batch is suppressed in one launch."""
+        cls = [t.detach().float() for t in cls_scores_3]
+        assert len(cls) == len(keypts_preds_3) == len(bbox_preds_3)
+        if nms and self._packed_ok(cls, img_metas, cfg):
+            det, label, kp, count = self.get_bboxes_packed(cls, bbox_preds_3, keypts_preds_3, img_metas, cfg, rescale)
+            counts = count.tolist()                      # the only device->host read of the post-processing
+            return [(det[b, :n], label[b, :n], kp[b, :n]) for b, n in enumerate(counts)]
+        bboxes, scores, kpts = self._decode(cls, bbox_preds_3, keypts_preds_3, img_metas, cfg, rescale)
+        return self.candidates_to_results(bboxes, scores, kpts, cfg, nms, batched_hard_nms=bboxes.is_cuda)
+
+    def get_bboxes_packed_tensor(self, cls_scores_1, cls_scores_2, cls_scores_3, keypts_preds_1, keypts_preds_2,
+                                 keypts_preds_3, bbox_preds_1, bbox_preds_2, bbox_preds_3, img_metas, cfg,
+                                 rescale=False):
+        """The batch's detections as ONE device tensor [B, max_per_img, 7 + 3K] -- columns: box (4), score, label,
+        count (repeated), landmarks -- produced without any host read (capturable in a HIP graph); None when the
+        packed path does not apply.  ``unpack_results`` splits its host copy per image."""
+        cls = [t.detach().float() for t in cls_scores_3]
+        if not self._packed_ok(cls, img_metas, cfg):
+            return None
+        return decode.pack_rows(*self.get_bboxes_packed(cls, bbox_preds_3, keypts_preds_3, img_metas, cfg, rescale))
 
 
 HEADS.register_alias('KGDetHead', RepPointsHeadKp3RepCas1AssignOnce)

@@ -164,8 +164,7 @@ class DeviceResults(object):
         from .detector import RepPointsDetectorKp
         unpack = self._unpack
         if unpack is None:
-            from .heads import RepPointsHeadKp3RepCas1AssignOnce
-            unpack = RepPointsHeadKp3RepCas1AssignOnce.unpack_results
+            from .decode import unpack_results as unpack
         # (bbox2result_kp reads nothing of its detector -- it is called without one here; it has to stay that way)
         return [RepPointsDetectorKp.bbox2result_kp(None, d.copy(), lab, k, self.num_classes)
                 for d, lab, k in unpack(self.rows.cpu().numpy())]

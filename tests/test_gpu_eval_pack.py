@@ -290,7 +290,7 @@ def test_a_tta_sample_and_a_sample_off_the_packed_path(demo, monkeypatch):
     got = single_gpu_test(model, tta, rescale=True, to_device=_to_dev, device_results=True)
     assert _assert_same_results(got.to_host(), want) > 0
     one = _Slice(demo['data'], [3])
-    monkeypatch.setattr(model.bbox_head, '_packed_ok', lambda *a, **k: False)      # (both runs decode image by image)
+    monkeypatch.setattr(model.bbox_head, '_packed_ok', lambda *a, **k: False)      # (both runs leave the fused NMS for the per-image results)
     want = single_gpu_test(model, one, rescale=True, to_device=_to_dev)
     got = single_gpu_test(model, one, rescale=True, to_device=_to_dev, device_results=True)
     assert _assert_same_results(got.to_host(), want) > 0
