@@ -995,6 +995,38 @@ int kgdet_coco_scatter_dets(const float *rows, int64_t N, int32_t M, int32_t W, 
                             const int64_t *start_bbox, const int64_t *start_kp, int32_t cut_bbox, int32_t cut_kp,
                             const kgdet_coco_packed_dets *out_bbox, const kgdet_coco_packed_dets *out_kp, int32_t *flags,
                             void *stream);
+/* results2json on the device (csrc/coco_json.hip): the text of the two result files, byte for byte what json.dump (default
+ * separators) writes for kpt2json's lists, from rows and from what kgdet_coco_order_dets left (vals, info; call it with
+ * img_slot = 0 .. N - 1, cat_of_label = 0 .. L - 1 and C = L so that no row is dropped for lack of ground truth).
+ * Record r = img_base[image] + k, every row with a label in [0, L):
+ *   bbox       {"image_id": I, "bbox": [x, y, w, h], "score": s, "category_id": c}
+ *   keypoints  {"image_id": I, "keypoints": [v0, ..., v(3K-1)], "score": s, "category_id": c}
+ * I = img_ids[image], c = cat_ids[label] (int64, non-negative); x y w h s from vals; v = rint(float64(value) * 10^d) / 10^d;
+ * each printed as repr of the double: [-] integer digits . fractional digits without trailing zeros, at least one; zero
+ * keeps its sign.  num_digits d in 1 .. 4; domain finite and |v| * 10^d < 2^40 (a value outside stands as 0.0).
+ * kgdet_coco_json_measure (one workgroup per image, one wave per row): len_bbox / len_kp int32 [n_records] = the byte length
+ * of record r of either kind, rec_src int64 [n_records] = image * M + row; n_records >= the sum of img_rows (entries no
+ * record owns are left as they are).  flags int32 [2], ADDED to: [0] landmark values of written rows outside the domain,
+ * [1] rows whose record index lies outside [0, n_records).
+ * kgdet_coco_json_write (one workgroup per record, the record assembled in LDS and stored 16 bytes at a time): offset int64
+ * [>= r1 + 1] = where record r begins in the file's body WITH the ", " that separates it from record r - 1, i.e. the
+ * exclusive scan of len[r] + (r > 0 ? 2 : 0).  Records r0 <= r < r1 of `kind` (0 bbox, 1 keypoints) are written to
+ * out + offset[r] - offset[r0]; range_bytes = offset[r1] - offset[r0] as the caller read it back, out_bytes the size of out.
+ * Nothing outside [out, out + range_bytes) is written; the enclosing [ and ] are the caller's.  A record whose text is not
+ * offset[r + 1] - offset[r] bytes long or lies outside the range is skipped and counted in flags[1].
+ * Refused before any launch (KGDET_E_SHAPE): num_digits outside [1, 4], W != 7 + 3K with K in [1, KGDET_COCO_JSON_MAX_K]
+ * (a record's LDS image, 144 + 51 K bytes, stays under 64 KiB), M outside [1, KGDET_COCO_ORDER_MAX_ROWS], L outside [1,
+ * KGDET_COCO_ORDER_MAX_LABELS], N outside [0, 2^31), a null pointer where data is required, r0 < 0, r1 < r0, r1 > N * M,
+ * out_bytes < range_bytes, a kind other than 0 / 1.  N == 0 or r0 == r1 is a no-op. */
+#define KGDET_COCO_JSON_MAX_K 1024
+int kgdet_coco_json_measure(const float *rows, int64_t N, int32_t M, int32_t W, const double *vals, const int32_t *info,
+                            const int64_t *img_base, const int64_t *img_ids, const int64_t *cat_ids, int32_t L,
+                            int32_t num_digits, int32_t *len_bbox, int32_t *len_kp, int64_t *rec_src, int64_t n_records,
+                            int32_t *flags, void *stream);
+int kgdet_coco_json_write(int32_t kind, const float *rows, int64_t N, int32_t M, int32_t W, const double *vals,
+                          const int64_t *rec_src, const int64_t *offset, const int64_t *img_ids, const int64_t *cat_ids,
+                          int32_t L, int32_t num_digits, int64_t r0, int64_t r1, int64_t range_bytes, uint8_t *out,
+                          int64_t out_bytes, int32_t *flags, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

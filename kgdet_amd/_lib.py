@@ -47,6 +47,7 @@ COCO_ACC_TILE = 1024    # KGDET_COCO_ACC_TILE: positions of a category's sequenc
 COCO_PACK_ROWS = 4      # KGDET_COCO_PACK_ROWS: landmark rows (waves) per workgroup
 COCO_ORDER_MAX_ROWS = 1024    # KGDET_COCO_ORDER_MAX_ROWS: detections per image kgdet_coco_order_dets ranks in LDS
 COCO_ORDER_MAX_LABELS = 64    # KGDET_COCO_ORDER_MAX_LABELS
+COCO_JSON_MAX_K = 1024        # KGDET_COCO_JSON_MAX_K: landmarks of a record kgdet_coco_json_write assembles in LDS
 
 
 class CocoPackedDets(ctypes.Structure):
@@ -125,6 +126,11 @@ def lib():
             L.kgdet_coco_order_dets.argtypes = [vp, i64, i32, i32, vp, vp, i32, i32, i64, i32, i32, i32] + [vp] * 7
             L.kgdet_coco_scatter_dets.argtypes = ([vp, i64, i32, i32, vp, i32, i64] + [vp] * 5 + [i32, i32]
                                                   + [ctypes.POINTER(CocoPackedDets)] * 2 + [vp, vp])
+        if hasattr(L, 'kgdet_coco_json_write'):
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_coco_json_measure.restype = L.kgdet_coco_json_write.restype = ctypes.c_int
+            L.kgdet_coco_json_measure.argtypes = [vp, i64, i32, i32] + [vp] * 5 + [i32, i32, vp, vp, vp, i64, vp, vp]
+            L.kgdet_coco_json_write.argtypes = [i32, vp, i64, i32, i32] + [vp] * 5 + [i32, i32, i64, i64, i64, vp, i64, vp, vp]
         _lib = L
     return _lib
 

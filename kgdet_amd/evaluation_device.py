@@ -20,6 +20,10 @@ similarities and four nested Python loops for the matching.  This module keeps i
   ``kgdet_coco_order_dets`` / ``kgdet_coco_scatter_dets`` (csrc/coco_pack_dets.hip): order, exact decimal rounding, cut and
   the landmark gather as kernels, ``kxy32`` a device tensor; ``pack_rows_restatement`` is their numpy restatement.
 
+* ``write_device_results_json`` / ``results2json_any``: ``results2json`` for a ``runner.DeviceResults`` -- the two result files,
+  byte for byte, formatted by ``kgdet_coco_json_measure`` / ``kgdet_coco_json_write`` (csrc/coco_json.hip) from the rows where
+  they lie; ``json_restatement`` is their numpy restatement.
+
 What the device computes differently from numpy is stated in DESIGN.md: box IoU is bit-identical; for OKS the exponent
 argument is bit-identical, ``exp`` and the order of the sum over the landmarks are the device's.
 """
@@ -1028,3 +1032,320 @@ def evaluate_results(dataset, results, result_types=('bbox', 'keypoints'), devic
             raise ValueError('the results hold no {!r} detections'.format(t))
         out[t] = evaluate_packed(packed_gt, packed[t], t, device, verbose, device_accumulate)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# results2json for results that stayed on the device (runner.DeviceResults; csrc/coco_json.hip)
+# ------------------------------------------------------------------------------------------------
+JSON_MAX_DIGITS = 4              # with 5 digits a non-zero value can fall below 1e-4, where repr switches to exponent form
+# bytes of text per launch, copy and f.write: two device and two page-locked host buffers of this size are held.  Chosen from
+# the sizes involved, not from a sweep: a landmark record is about 8.7 kB, so 64 MiB is some 7 700 records = 7 700 workgroups
+# per launch (30 per CU), a copy of a few milliseconds over the host link, and a file write long enough for the page cache
+# to take it in one piece; 4 x 64 MiB is small beside the rows themselves (11 GB at 32 000 x 100).
+JSON_CHUNK_BYTES = 64 << 20
+
+
+def format_decimals(q, negative, num_digits):
+    """``repr`` of the doubles ``(-1)**negative * q / 10**num_digits`` as a list of str, from the integers alone: an optional
+    ``-``, the integer part's digits, ``.``, the ``num_digits`` fractional digits without their trailing zeros but at least
+    one.  For ``q < 2**40 + 1`` and ``1 <= num_digits <= 4`` the digits are at most 15 significant and the value is 0 or at
+    least 1e-4, so this positional text is the shortest one that reads back as the same double -- what ``float.__repr__``
+    prints (held to it by tests/test_json_refs.py)."""
+    P = 10 ** num_digits
+    out = []
+    for v, neg in zip(np.asarray(q, dtype=np.int64).reshape(-1).tolist(), np.asarray(negative, dtype=bool).reshape(-1).tolist()):
+        ip, fr = divmod(v, P)
+        out.append('%s%d.%s' % ('-' if neg else '', ip, ('%0*d' % (num_digits, fr)).rstrip('0') or '0'))
+    return out
+
+
+def decimals_of_rounded(values, num_digits):
+    """(q int64, negative bool) of doubles that are already n / 10**d (``round_half_even_restatement``'s): n = rint(|x| * 10**d),
+    the sign is the double's sign bit -- a negative value that rounded to zero stays ``-0.0``"""
+    x = np.asarray(values, dtype=np.float64)
+    return np.rint(np.abs(x) * np.float64(10.0 ** num_digits)).astype(np.int64), np.signbit(x)
+
+
+def decimals_of_landmarks(values, num_digits):
+    """(q int64, negative bool, values outside the domain) for float32 landmark values: ``np.round(float64(v), d)`` is
+    ``rint(v * 10**d) / 10**d`` and the float32 x 10**d product is exact in float64, so q = rint(|v| * 10**d) and the sign is
+    v's sign bit.  A value that is not finite or with ``|v| * 10**d >= 2**40`` is counted and stands as 0."""
+    v = np.asarray(values, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        p = np.abs(v) * np.float64(10.0 ** num_digits)
+        bad = ~(p < ROUND_LIMIT)
+    q = np.rint(np.where(bad, 0.0, p)).astype(np.int64)
+    return q, np.signbit(v) & ~bad, int(np.count_nonzero(bad))
+
+
+def _json_tables(dataset, N, L):
+    """(image ids int64 [N], category ids int64 [L]) as the records print them; ``ValueError`` for what the kernels do not take"""
+    from . import _lib
+    if N != len(dataset):
+        raise ValueError('%d result blocks for a dataset of %d samples' % (N, len(dataset)))
+    if not 1 <= L <= min(len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS):
+        raise ValueError('%d labels: the dataset names %d categories, the kernels take up to %d'
+                         % (L, len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS))
+    tables = []
+    for what, ids in (('image', list(dataset.img_ids)[:N]), ('category', list(dataset.cat_ids)[:L])):
+        for v in ids:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 63:
+                raise ValueError('%s id %r: the device route prints non-negative integers below 2**63' % (what, v))
+        tables.append(np.asarray([int(v) for v in ids], dtype=np.int64).reshape(-1))
+    return tables
+
+
+def _json_records(dataset, rows, num_digits=4, num_labels=None):
+    """([bbox record bytes], [keypoints record bytes]) in id order: what ``json_restatement`` joins"""
+    if not isinstance(rows, np.ndarray):
+        rows = rows.cpu().numpy()
+    if isinstance(num_digits, bool) or not isinstance(num_digits, (int, np.integer)) or not 1 <= num_digits <= JSON_MAX_DIGITS:
+        raise ValueError('num_digits %r (1 .. %d)' % (num_digits, JSON_MAX_DIGITS))
+    N, M, W = rows.shape
+    K = (W - 7) // 3
+    if W != 7 + 3 * K or K < 1:
+        raise ValueError('rows of %d floats (7 + 3K)' % W)
+    L = len(dataset.cat_ids) if num_labels is None else int(num_labels)
+    img_ids, cat_ids = _json_tables(dataset, N, L)
+    box_out, kpt_out, n_bad = [], [], 0
+    for n in range(N):
+        cf = rows[n, 0, 6]
+        if not (cf >= 0 and cf < M + 1):
+            raise ValueError('sample %d: count %r outside [0, %d]' % (n, cf, M))
+        r = rows[n, :int(cf)]
+        with np.errstate(invalid='ignore'):
+            valid = (r[:, 5] > -1) & (r[:, 5] < L)
+        r = r[valid]
+        r = r[np.argsort(r[:, 5].astype(np.int64), kind='mergesort')]          # label ascending, then row order
+        b = r[:, :5].astype(np.float64)
+        xywhs, bad = _round_half_even(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1, b[:, 4]], axis=1),
+                                      num_digits)
+        q, neg, bad_k = decimals_of_landmarks(r[:, 7:], num_digits)
+        n_bad += bad + bad_k
+        if bad or bad_k:
+            continue
+        box_text = format_decimals(*decimals_of_rounded(xywhs, num_digits), num_digits)
+        kpt_text = format_decimals(q, neg, num_digits)
+        for i in range(len(r)):
+            x, y, w, h, s = box_text[5 * i:5 * i + 5]
+            tail = '], "score": %s, "category_id": %d}' % (s, cat_ids[int(r[i, 5])])
+            box_out.append(('{"image_id": %d, "bbox": [%s, %s, %s, %s' % (img_ids[n], x, y, w, h) + tail).encode('ascii'))
+            kpt_out.append(('{"image_id": %d, "keypoints": [%s' % (img_ids[n], ', '.join(kpt_text[3 * K * i:3 * K * (i + 1)]))
+                            + tail).encode('ascii'))
+    if n_bad:
+        raise ValueError('%d values are not finite or reach 2**40 / 10**%d' % (n_bad, num_digits))
+    return box_out, kpt_out
+
+
+def json_restatement(dataset, rows, num_digits=4, num_labels=None):
+    """(contents of P.bbox.json, contents of P.keypoints.json) as bytes: what ``evaluation.results2json(dataset, dev.to_host(),
+    P)`` writes for ``rows`` float32 [N, M, 7 + 3K] (``runner.DeviceResults.rows``, a host copy), computed from the rows with
+    the formatter rule written out (``format_decimals``) -- no ``json`` and no ``repr`` of a float.  Per image the first
+    ``count`` rows with a label in [0, L), label ascending and in row order inside a label; xywh and score rounded like
+    Python's ``round`` (``round_half_even_restatement``), landmark values like ``np.round``.  The reference of
+    ``kgdet_coco_json_measure`` / ``kgdet_coco_json_write``; held to ``results2json`` by tests/test_json_refs.py.
+    ``ValueError``: ``num_digits`` outside 1 .. 4, a value outside the domain, a count outside [0, M], more labels than
+    ``dataset.cat_ids`` (``num_labels``: the detector's, None = the dataset's), ids that are not non-negative ints."""
+    box, kpt = _json_records(dataset, rows, num_digits, num_labels)
+    return b'[' + b', '.join(box) + b']', b'[' + b', '.join(kpt) + b']'
+
+
+def _json_files(out_file):
+    files = {'bbox': '{}.bbox.json'.format(out_file), 'keypoints': '{}.keypoints.json'.format(out_file)}
+    files['proposal'] = files['bbox']
+    return files
+
+
+class _TempFiles(object):
+    """the two result files under temporary names beside their targets: renamed by ``commit()``, removed on any exit
+    without it"""
+
+    def __init__(self, files):
+        self.final = {k: files[k] for k in ('bbox', 'keypoints')}
+        self.temp = {k: '%s.tmp-%d' % (p, os.getpid()) for k, p in self.final.items()}
+        self.done = False
+
+    def __enter__(self):
+        return self
+
+    def commit(self):
+        for k in ('bbox', 'keypoints'):
+            os.replace(self.temp[k], self.final[k])
+        self.done = True
+
+    def __exit__(self, *exc):
+        if not self.done:
+            for p in self.temp.values():
+                if os.path.exists(p):
+                    os.remove(p)
+        return False
+
+
+def _json_chunks(off, n_records, chunk_bytes):
+    """record ranges [r0, r1) of at most ``chunk_bytes`` each, greedily, from the records' offsets (int64 [>= n_records + 1])"""
+    bounds, r = [], 0
+    while r < n_records:
+        nxt = min(int(np.searchsorted(off[:n_records + 1], off[r] + chunk_bytes, side='right')) - 1, n_records)
+        assert nxt > r
+        bounds.append((r, nxt))
+        r = nxt
+    return bounds
+
+
+def write_device_results_json(dataset, dev_results, out_file, num_digits=4, chunk_bytes=JSON_CHUNK_BYTES, device=None,
+                              timings=None):
+    """``evaluation.results2json(dataset, dev_results.to_host(), out_file)`` -- the same two files, byte for byte, and the
+    same dict of their names -- without the host list: ``kgdet_coco_order_dets`` (identity tables, so no row is dropped
+    for lack of ground truth) and ``kgdet_coco_json_measure`` on ``dev_results.rows`` where it lies, one ``torch.cumsum``
+    per kind, ONE read-back (flags, record count and the records' byte offsets: 16 bytes per detection against 8.8 kB of
+    text), then per kind a loop over chunks of whole records of at most ``chunk_bytes``: ``kgdet_coco_json_write`` into one of
+    two device buffers, a non-blocking copy into one of two page-locked host buffers with an event behind it, and ``f.write``
+    of that buffer while the next chunk's kernel and copy run; the write kernel's own flag word (records that disagree with
+    their offsets) is read once more before the rename.  Only the calling thread touches HIP.  ``chunk_bytes``
+    defaults to ``JSON_CHUNK_BYTES`` (see there for what it was chosen from).  The files are written under temporary names
+    and renamed when both are complete.  ``dataset`` needs ``img_ids``, ``cat_ids`` and ``__len__`` only; the results are not
+    released.  ``device``: None = where the rows are; rows on the CPU (or none) take ``json_restatement``.  ``timings``: a dict
+    that receives seconds per stage (``order_measure_s``, ``kernel_s`` and ``copy_s`` from events, ``file_s``) and ``bytes``.
+    ``ValueError``, with no file under a final name: released results, ``num_digits`` outside 1 .. 4, a value outside the
+    domain (finite, ``|v| * 10**d < 2**40``), a count outside [0, M], more labels than ``dataset.cat_ids`` or than the order
+    kernel's 64, more than its 1024 rows per image or more landmarks than a record's LDS image holds, ids that are not
+    non-negative ints below 2**63, a record longer than ``chunk_bytes``."""
+    import time
+    import torch
+    from . import _lib
+    rows = dev_results.rows
+    if rows is None:
+        raise ValueError('the device results were released')
+    if isinstance(num_digits, bool) or not isinstance(num_digits, (int, np.integer)) or not 1 <= num_digits <= JSON_MAX_DIGITS:
+        raise ValueError('num_digits %r (1 .. %d)' % (num_digits, JSON_MAX_DIGITS))
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes < 1:
+        raise ValueError('chunk_bytes %r' % (chunk_bytes,))
+    files = _json_files(out_file)
+    L = int(dev_results.num_classes) - 1
+    if device is not None and str(device) != 'cpu':
+        rows = rows.to(torch.device(device))
+    if timings is None:
+        timings = {}
+    timings.update(order_measure_s=0.0, kernel_s=0.0, copy_s=0.0, file_s=0.0, bytes=0)
+    if not rows.is_cuda or rows.shape[0] == 0:
+        box, kpt = _json_records(dataset, rows, num_digits, num_labels=L)
+        longest = max([len(r) + 2 for r in box[1:] + kpt[1:]] + [len(r) for r in box[:1] + kpt[:1]] + [0])
+        if longest > chunk_bytes:
+            raise ValueError('a record of %d bytes does not fit chunk_bytes = %d' % (longest, chunk_bytes))
+        with _TempFiles(files) as tmp:
+            for kind, recs in (('bbox', box), ('keypoints', kpt)):
+                with open(tmp.temp[kind], 'wb') as f:
+                    f.write(b'[' + b', '.join(recs) + b']')
+                timings['bytes'] += os.path.getsize(tmp.temp[kind])
+            tmp.commit()
+        return files
+    rows = rows.contiguous()
+    N, M, W = rows.shape
+    K = (W - 7) // 3
+    if W != 7 + 3 * K or not 1 <= K <= _lib.COCO_JSON_MAX_K:
+        raise ValueError('rows of %d floats (7 + 3K, K = 1 .. %d)' % (W, _lib.COCO_JSON_MAX_K))
+    if M > _lib.COCO_ORDER_MAX_ROWS:
+        raise ValueError('%d detections per image: the order kernel ranks up to %d' % (M, _lib.COCO_ORDER_MAX_ROWS))
+    img_ids, cat_ids = _json_tables(dataset, N, L)
+    lib = _lib.lib()
+    dev = rows.device
+    i32, i64, p = ctypes.c_int32, ctypes.c_int64, _lib.ptr
+    cap = N * M
+    clock = time.perf_counter
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream()
+        t0 = clock()
+        slot_t = torch.arange(N, dtype=torch.int32, device=dev)
+        col_t = torch.arange(L, dtype=torch.int32, device=dev)
+        img_t, cat_t = torch.from_numpy(img_ids).to(dev), torch.from_numpy(cat_ids).to(dev)
+        vals = torch.empty((N, M, 6), dtype=torch.float64, device=dev)
+        info = torch.empty((N, M, 3), dtype=torch.int32, device=dev)
+        img_rows = torch.empty((N,), dtype=torch.int32, device=dev)
+        cnt = torch.empty((2, N * L), dtype=torch.int32, device=dev)
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        _lib.check(lib.kgdet_coco_order_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), p(col_t), i32(L), i32(L), i64(N * L),
+                                             i32(num_digits), i32(MAX_DETS['bbox']), i32(MAX_DETS['keypoints']), p(vals), p(info),
+                                             p(img_rows), p(cnt[0]), p(cnt[1]), p(flags), stream), 'kgdet_coco_order_dets')
+        del cnt
+        total_rows = torch.cumsum(img_rows, dim=0, dtype=torch.int64)
+        img_base = total_rows - img_rows
+        lens = torch.zeros((2, cap), dtype=torch.int32, device=dev)
+        rec_src = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+        _lib.check(lib.kgdet_coco_json_measure(p(rows), i64(N), i32(M), i32(W), p(vals), p(info), p(img_base), p(img_t), p(cat_t),
+                                               i32(L), i32(num_digits), p(lens[0]), p(lens[1]), p(rec_src), i64(cap), p(flags),
+                                               stream), 'kgdet_coco_json_measure')
+        # where record r begins, with the ", " in front of every record but the first: the exclusive scan of len + (r > 0) * 2
+        offset = torch.zeros((2, cap + 1), dtype=torch.int64, device=dev)
+        offset[:, 1:] = torch.cumsum(lens, dim=1, dtype=torch.int64) + 2 * torch.arange(cap, dtype=torch.int64, device=dev)
+        del lens, info
+        host = torch.cat([flags.to(torch.int64), total_rows[-1:], offset.reshape(-1)]).cpu().numpy()       # (the one read-back)
+        bad_value, bad_layout, R = (int(v) for v in host[:3])
+        off = host[3:].reshape(2, cap + 1)
+        timings['order_measure_s'] = clock() - t0
+        if bad_value:
+            raise ValueError('%d values are not finite or reach 2**40 / 10**%d' % (bad_value, num_digits))
+        if bad_layout:
+            raise ValueError('%d samples with a count outside [0, %d] (or rows outside the record table)' % (bad_layout, M))
+        longest = int(np.diff(off[:, :R + 1], axis=1).max()) if R else 0
+        if longest > chunk_bytes:
+            raise ValueError('a record of %d bytes does not fit chunk_bytes = %d' % (longest, chunk_bytes))
+        size = min(chunk_bytes, max(int(off[:, R].max()), 1))
+        d_buf = [torch.empty(size, dtype=torch.uint8, device=dev) for _ in range(2)]
+        h_buf = [torch.empty(size, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        h_view = [memoryview(b.numpy()) for b in h_buf]
+        events = []                                                 # (before kernel, after kernel, after copy) per chunk
+        with _TempFiles(files) as tmp:
+            for kind, name in enumerate(('bbox', 'keypoints')):
+                chunks = _json_chunks(off[kind], R, chunk_bytes)
+
+                def issue(c):
+                    r0, r1 = chunks[c]
+                    nbytes = int(off[kind, r1] - off[kind, r0])
+                    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    ev[0].record()
+                    _lib.check(lib.kgdet_coco_json_write(i32(kind), p(rows), i64(N), i32(M), i32(W), p(vals), p(rec_src),
+                                                         p(offset[kind]), p(img_t), p(cat_t), i32(L), i32(num_digits), i64(r0),
+                                                         i64(r1), i64(nbytes), p(d_buf[c % 2]), i64(size), p(flags), stream),
+                               'kgdet_coco_json_write')
+                    ev[1].record()
+                    h_buf[c % 2][:nbytes].copy_(d_buf[c % 2][:nbytes], non_blocking=True)
+                    ev[2].record()
+                    events.append(ev)
+                    return ev[2], nbytes
+
+                with open(tmp.temp[name], 'wb') as f:
+                    f.write(b'[')
+                    pending = issue(0) if chunks else None
+                    for c in range(len(chunks)):
+                        done, nbytes = pending
+                        pending = issue(c + 1) if c + 1 < len(chunks) else None
+                        done.synchronize()
+                        t0 = clock()
+                        f.write(h_view[c % 2][:nbytes])
+                        timings['file_s'] += clock() - t0
+                        timings['bytes'] += nbytes
+                    f.write(b']')
+                    timings['bytes'] += 2
+            if int(flags[1]):
+                raise RuntimeError('kgdet_coco_json_write: records disagree with their offsets (measure and write differ)')
+            tmp.commit()
+        for ev in events:
+            timings['kernel_s'] += ev[0].elapsed_time(ev[1]) * 1e-3
+            timings['copy_s'] += ev[1].elapsed_time(ev[2]) * 1e-3
+    return files
+
+
+def results2json_any(dataset, results, out_file):
+    """``evaluation.results2json`` for whatever ``single_gpu_test`` returned: a ``runner.DeviceResults`` takes the device
+    route (``write_device_results_json``) and, on its ``ValueError``, ``results2json`` of its ``to_host()`` list with one warning
+    that names the reason; a list takes ``results2json`` as it is.  -> the dict of file names"""
+    from .evaluation import results2json
+    if not _is_device_results(results):
+        return results2json(dataset, results, out_file)
+    try:
+        return write_device_results_json(dataset, results, out_file)
+    except ValueError as e:
+        import warnings
+        warnings.warn('the result files are written on the host instead (the slow route): %s' % e, RuntimeWarning)
+        return results2json(dataset, results.to_host(), out_file)

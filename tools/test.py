@@ -6,8 +6,9 @@
 ``cfg.data.test`` goes through ``runner.single_gpu_test``: ``--workers`` threads decode and prepare the upcoming images
 (default ``cfg.data.workers_per_gpu``), ``--imgs-per-gpu`` images of one shape share a forward pass, ``--device-preprocess``
 runs the input transform on the GPU, ``--device-results`` keeps the detections in device memory until they are evaluated.
-``--json_out P`` writes ``P.bbox.json`` / ``P.keypoints.json`` through ``evaluation.results2json`` and evaluates those files
-with ``coco_eval``; without it ``--eval`` evaluates the results where they lie (``evaluation_device.evaluate_results``).  A
+``--json_out P`` writes ``P.bbox.json`` / ``P.keypoints.json`` through ``evaluation.results2json`` -- with ``--device-results``
+from the rows in device memory (``evaluation_device.results2json_any``: the same bytes, formatted by kernels) -- and evaluates
+those files with ``coco_eval``; without it ``--eval`` evaluates the results where they lie (``evaluation_device.evaluate_results``).  A
 ``--launcher`` other than ``none`` is refused: the multi-rank launch is not part of this tool."""
 import argparse
 import os
@@ -56,9 +57,8 @@ def main(argv=None):
     stats = None
     if args.json_out:
         out = args.json_out[:-5] if args.json_out.endswith('.json') else args.json_out
-        host = results.to_host() if args.device_results else results
         print('writing results to {}'.format(out))
-        files = evaluation.results2json(dataset, host, out)
+        files = evaluation_device.results2json_any(dataset, results, out)
         if args.eval:
             print('Starting evaluate {}'.format(' and '.join(args.eval)))
             stats = evaluation.coco_eval(files, args.eval, dataset.coco, device='cuda:0')
