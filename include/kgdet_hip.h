@@ -1027,6 +1027,34 @@ int kgdet_coco_json_write(int32_t kind, const float *rows, int64_t N, int32_t M,
                           const int64_t *rec_src, const int64_t *offset, const int64_t *img_ids, const int64_t *cat_ids,
                           int32_t L, int32_t num_digits, int64_t r0, int64_t r1, int64_t range_bytes, uint8_t *out,
                           int64_t out_bytes, int32_t *flags, void *stream);
+/* Detections and landmarks drawn on images (csrc/draw.hip; kgdet_amd/visualize.py: DeviceDrawer), bit for bit the picture
+ * visualize.draw_restatement defines: per drawn row (score > score_thr, an integer label in [0, L), a finite box) the box
+ * outline of `thickness`, with `contour` the capsules of width `line_width` between consecutive visible landmarks, the
+ * landmark discs of `radius` (in kpt_color 0xRRGGBB, or the class colour for -1) and the label "name|d.dd" in 5 x 7 glyphs
+ * scaled by `font_scale`; a pixel shows the covering primitive of the greatest (row, layer), else its source value.
+ * One launch draws n <= KGDET_DRAW_MAX_IMAGES images of different sizes, out of place, between two flat uint8 buffers in
+ * device memory (RGB, H x W x 3, rows packed): table is a HOST array int64 [n][4] = (source offset, destination offset, H, W)
+ * and row_block a HOST array int32 [n] = the image's block of rows [N, M, W7 = 7 + 3K] (device, the layout of
+ * get_bboxes_packed_tensor; the count is column 6 of the block's row 0, cut to [0, M]).  Both are read before the launch and
+ * travel as kernel arguments, as the jobs of kgdet_image_preprocess do, so every size and offset is checked here.  Device
+ * tables: colors uint8 [L][3]; name_bytes uint8 [name_total] with name_off int32 [L + 1] (a name is at most 255 bytes);
+ * ranges int32 [L][2] = the landmarks [a, b) of a label, or NULL for all K; glyphs uint8 [256][7] = the row masks of every
+ * byte, bit 4 the left column.  One wave per tile of 64 x 16 pixels; no atomics, no workspace, nothing read back.
+ * Refused before the launch with nothing written (KGDET_E_SHAPE): n outside [0, KGDET_DRAW_MAX_IMAGES], M outside [1,
+ * KGDET_DRAW_MAX_ROWS], W7 != 7 + 3K with K in [1, KGDET_DRAW_MAX_K], L outside [1, KGDET_DRAW_MAX_LABELS], H or W outside
+ * [1, 8192], thickness or radius outside [1, 64], line_width outside [1, 16], font_scale outside [1, 8], kpt_color outside
+ * [-1, 0xffffff], an image outside its buffer, a row block outside [0, N), overlapping buffers, a null pointer where data is
+ * required.  n == 0 is a no-op.  Destination ranges of different images must not overlap (not checked). */
+#define KGDET_DRAW_MAX_IMAGES 32
+#define KGDET_DRAW_MAX_ROWS 1024
+#define KGDET_DRAW_MAX_K 1024
+#define KGDET_DRAW_MAX_LABELS 64
+int kgdet_draw_detections(const uint8_t *src, int64_t src_bytes, uint8_t *dst, int64_t dst_bytes, const int64_t *table,
+                          const int32_t *row_block, int32_t n, const float *rows, int64_t N, int32_t M, int32_t W7,
+                          const uint8_t *colors, int32_t L, const uint8_t *name_bytes, const int32_t *name_off,
+                          int32_t name_total, const int32_t *ranges, const uint8_t *glyphs, float score_thr, int32_t thickness,
+                          int32_t radius, int32_t contour, int32_t line_width, int32_t font_scale, int32_t kpt_color,
+                          void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

@@ -48,6 +48,7 @@ COCO_PACK_ROWS = 4      # KGDET_COCO_PACK_ROWS: landmark rows (waves) per workgr
 COCO_ORDER_MAX_ROWS = 1024    # KGDET_COCO_ORDER_MAX_ROWS: detections per image kgdet_coco_order_dets ranks in LDS
 COCO_ORDER_MAX_LABELS = 64    # KGDET_COCO_ORDER_MAX_LABELS
 COCO_JSON_MAX_K = 1024        # KGDET_COCO_JSON_MAX_K: landmarks of a record kgdet_coco_json_write assembles in LDS
+DRAW_MAX_IMAGES, DRAW_MAX_ROWS, DRAW_MAX_K, DRAW_MAX_LABELS = 32, 1024, 1024, 64    # KGDET_DRAW_MAX_*: kgdet_draw_detections
 
 
 class CocoPackedDets(ctypes.Structure):
@@ -131,6 +132,11 @@ def lib():
             L.kgdet_coco_json_measure.restype = L.kgdet_coco_json_write.restype = ctypes.c_int
             L.kgdet_coco_json_measure.argtypes = [vp, i64, i32, i32] + [vp] * 5 + [i32, i32, vp, vp, vp, i64, vp, vp]
             L.kgdet_coco_json_write.argtypes = [i32, vp, i64, i32, i32] + [vp] * 5 + [i32, i32, i64, i64, i64, vp, i64, vp, vp]
+        if hasattr(L, 'kgdet_draw_detections'):      # visualize.py: host tables, int64 sizes and a float among the arguments
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_draw_detections.restype = ctypes.c_int
+            L.kgdet_draw_detections.argtypes = ([vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, vp, i32, vp, vp, i32, vp, vp,
+                                                 ctypes.c_float] + [i32] * 6 + [vp])
         _lib = L
     return _lib
 

@@ -1,5 +1,6 @@
 """Entry points that run a config end to end, for one process and one GPU: ``mmdet/apis/train.py`` (``train_detector``,
-``set_random_seed``) and ``mmdet/apis/inference.py`` (``init_detector``, ``inference_detector``; no drawing of results).
+``set_random_seed``) and ``mmdet/apis/inference.py`` (``init_detector``, ``inference_detector``, and ``show_result``, which
+``visualize`` draws -- landmarks included -- on the GPU or, without one, with its numpy restatement).
 ``tools/train.py`` and ``tools/test.py`` are thin command lines over these and ``runner.single_gpu_test``."""
 import json
 import os
@@ -14,6 +15,7 @@ from .checkpoint import load_checkpoint
 from .loader import build_dataloader
 from .registry import Config, ConfigDict, build_detector
 from .runner import Runner, build_optimizer, single_gpu_test
+from .visualize import show_result  # noqa: F401  (mmdet.apis.show_result)
 
 
 def set_random_seed(seed):

@@ -292,6 +292,32 @@ class RepPointsDetectorKp(nn.Module):
             return self.forward_train(img, img_meta, **kwargs)
         return self.forward_test(img, img_meta, **kwargs)
 
+    def show_result(self, data, result, img_norm_cfg, dataset=None, score_thr=0.3):
+        """base.py:90-142 without the window: ``data['img'][0]`` (one test sample's normalised tensor, [3, H, W] or collated
+        [B, 3, H, W], with its metas in ``data['img_meta'][0]``) is denormalised, cut to ``img_shape`` and drawn with ``result``
+        as it stands (not rescaled: a result of ``rescale=False`` lies in this frame), landmarks included -> the list of uint8
+        RGB arrays.  ``dataset``: None for ``self.CLASSES``, or a sequence of class names; a dataset-name string (the
+        reference's ``get_classes``) raises ``TypeError``."""
+        from .visualize import denormalize, show_result
+        if dataset is None:
+            class_names = self.CLASSES
+        elif isinstance(dataset, (list, tuple)):
+            class_names = dataset
+        else:
+            raise TypeError('dataset must be a valid type, but got {} (a sequence of class names, or None)'.format(type(dataset)))
+        imgs, metas = data['img'][0], data['img_meta'][0]
+        if imgs.dim() == 3:
+            imgs, metas = imgs[None], [metas]
+        elif isinstance(metas, dict):
+            metas = [metas]
+        results = result if isinstance(result, list) else [result] * len(metas)
+        out = []
+        for img, meta, res in zip(imgs.float().cpu().numpy(), metas, results):
+            h, w = meta['img_shape'][:2]
+            shown = denormalize(img, **img_norm_cfg)[:h, :w]
+            out.append(show_result(np.ascontiguousarray(shown), res, class_names, score_thr=score_thr))
+        return out
+
 
 def merge_aug_results_kp(aug_bboxes, aug_scores, aug_kpts, img_metas):
     """The pure-torch statement of the test-time merge (upstream ``merge_aug_results`` + ``bbox_mapping_back``,

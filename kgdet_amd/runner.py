@@ -227,28 +227,30 @@ class _Prefetched(object):
         self.pool.shutdown(wait=True, cancel_futures=True)
 
 
-def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None, workers=0):
+def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None, workers=0,
+             show=None):
     """results of the samples ``indices`` in that order.  imgs_per_gpu == 1: the reference's call, one image per forward
     (``model(return_loss=False, rescale=..., **data)``, tools/test.py:25-28); > 1: runs of consecutive samples with identical
     tensor shapes and one augmentation go through ``simple_test_batch`` together (the same per-image results: nothing in
     backbone / neck / head / decode / NMS mixes the images of a batch).  ``device_preprocess``: the input transform runs on the
     model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then).  ``workers`` > 0: the samples are
-    prepared ahead in that many threads (``_Prefetched``) and consumed in the same order -- the same calls, the same results."""
+    prepared ahead in that many threads (``_Prefetched``) and consumed in the same order -- the same calls, the same results.
+    ``show``: a ``_Show`` that draws every group's images once its detections exist."""
     if workers < 0:
         raise ValueError('workers is >= 0, got %r' % (workers,))
     if workers:
         fn = dataset.prepare_test_raw if device_preprocess else dataset.__getitem__
         ahead = _Prefetched(fn, indices, workers)
         try:
-            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead)
+            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show)
         finally:
             ahead.close()
-    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None)
+    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None, show)
 
 
-def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead):
+def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show=None):
     if device_preprocess:
-        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead)
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead, show)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
@@ -280,11 +282,13 @@ def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device
                     sink.batch(model, img, [g['img_meta'][0] for g in group], rescale)
                 else:
                     results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
+        if show is not None:
+            show.group(indices[i:i + len(group)], None, results, sink)
         i += len(group)
     return results
 
 
-def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None):
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None, show=None):
     """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
     planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
     ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
@@ -319,28 +323,88 @@ def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None,
                     sink.batch(model, img, [g['img_meta'][0] for g in group], rescale)
                 else:
                     results.extend(model.simple_test_batch(img, [g['img_meta'][0] for g in group], rescale=rescale))
+        if show is not None:
+            show.group(indices[i:i + len(group)], [g['raw'] for g in group], results, sink)
         i += len(group)
     return results
 
 
+class _Show(object):
+    """``single_gpu_test(..., show_dir=...)``: once a group's detections exist, its original-size images -- ``raws``, or
+    ``dataset.load_image`` -- are drawn in one launch (``visualize.DeviceDrawer``) from the group's rows: the slice of the
+    sink's device tensor with ``device_results``, else the results just computed, packed and uploaded.  Only the finished
+    pictures come back to the host, where ``visualize.PictureWriter``'s threads encode them into
+    ``show_dir/<basename of the image file><ext>``."""
+
+    def __init__(self, model, dataset, show_dir, score_thr, ext, workers):
+        from .visualize import PictureWriter
+        target = model.module if hasattr(model, 'module') else model
+        self.dataset, self.score_thr = dataset, score_thr
+        self.device = next(target.parameters()).device
+        L = target.bbox_head.num_classes - 1
+        names = list(getattr(target, 'CLASSES', None) or getattr(dataset, 'CLASSES', None) or [])
+        self.names = names if len(names) == L else ['%d' % c for c in range(L)]
+        self.drawers = {}                     # by K: an image without detections comes as rows of one landmark
+        self.writer = PictureWriter(show_dir, workers, ext)
+
+    def name(self, idx):
+        filename = self.dataset.img_infos[idx].get('filename')
+        return os.path.basename(filename) if filename else 'image_%06d' % idx
+
+    def group(self, idxs, raws, results, sink):
+        from .visualize import DeviceDrawer, default_ranges, stack_result_rows
+        n = len(idxs)
+        block = stack_result_rows(results[-n:]) if sink is None else sink.rows[sink.at - n:sink.at]
+        K = (block.shape[2] - 7) // 3
+        if K not in self.drawers:
+            self.drawers[K] = DeviceDrawer(self.names, landmark_ranges=default_ranges(len(self.names), K), score_thr=self.score_thr,
+                                           device=self.device)
+        if raws is None:
+            raws = [self.dataset.load_image(i) for i in idxs]
+        for idx, picture in zip(idxs, self.drawers[K](raws, block, to_host=True)):
+            self.writer.put(picture, self.name(idx))
+
+    def close(self, failed=False):
+        self.writer.close(failed)
+
+
 def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False,
-                    device_results=False, workers=0):
+                    device_results=False, workers=0, show_dir=None, show_score_thr=0.3, show_ext='.jpg'):
     """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
     resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
     used then) instead of ``dataset[i]``'s host transform; same result format and order.  ``device_results``: the
     detections stay on the device -- a ``DeviceResults`` comes back instead of the list (its ``to_host()`` IS that list): no
     download and no per-class split per batch.  ``NotImplementedError`` for ``test_cfg.max_per_img <= 0`` (before the run) or
     an image with more detections than that.  ``workers``: threads that decode and prepare the upcoming samples (``_test_on``);
-    0 prepares each sample inline, as the reference's loop does."""
+    0 prepares each sample inline, as the reference's loop does.  ``show_dir`` (the reference's ``--show``, into files): every
+    image is drawn at its original size with the detections above ``show_score_thr`` (``_Show``) and written to
+    ``show_dir/<basename of the image file><show_ext>`` ('.jpg' at quality 90, or '.png') by ``workers`` threads, at least 1, at
+    most 16; what the call returns does not change.  It needs ``rescale=True`` (``ValueError`` before the run); a writer's
+    exception is re-raised, and the threads are gone when the call returns or raises."""
+    if show_dir is None:
+        return _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, None)
+    if not rescale:
+        raise ValueError('show_dir draws on the original images: it needs rescale=True')
+    show = _Show(model, dataset, show_dir, show_score_thr, show_ext, workers)
+    failed = True
+    try:
+        out = _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show)
+        failed = False
+    finally:
+        show.close(failed)
+    return out
+
+
+def _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show):
     if not device_results:
         return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess,
-                        workers=workers)
+                        workers=workers, show=show)
     target = model.module if hasattr(model, 'module') else model
     M = int(target.test_cfg.max_per_img)
     if M <= 0:
         raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
     sink = _RowSink(len(dataset))
-    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink, workers)
+    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink, workers, show)
     rows = sink.rows
     if rows is None:                            # (an empty dataset)
         rows = torch.empty((0, M, 10), dtype=torch.float32, device=next(target.parameters()).device)
