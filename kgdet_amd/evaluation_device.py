@@ -15,19 +15,21 @@ similarities and four nested Python loops for the matching.  This module keeps i
   outputs, vectorised per (category, area range, max_dets); ``summarize()`` is ``CocoEvaluator``'s.
 * ``pack_test_results(..., lazy_landmarks=True)``: the landmark rows stay float32 on the host and are rounded, with their
   extents, by ``kgdet_coco_pack_landmarks`` chunk by chunk (``materialize`` is the numpy route).
-
 * ``pack_device_results``: the packing of a ``runner.DeviceResults`` -- detections that never left the device -- by
   ``kgdet_coco_order_dets`` / ``kgdet_coco_scatter_dets`` (csrc/coco_pack_dets.hip): order, exact decimal rounding, cut and
   the landmark gather as kernels, ``kxy32`` a device tensor; ``pack_rows_restatement`` is their numpy restatement.
-
 * ``write_device_results_json`` / ``results2json_any``: ``results2json`` for a ``runner.DeviceResults`` -- the two result files,
   byte for byte, formatted by ``kgdet_coco_json_measure`` / ``kgdet_coco_json_write`` (csrc/coco_json.hip) from the rows where
   they lie; ``json_restatement`` is their numpy restatement.
+* What those two routes and their restatements share is written once: ``_row_block`` (what a rows block is, with every check
+  of it and of ``num_digits``), ``_image_rows`` (the restatements' walk over an image), ``_order_rows_on_device`` (the order
+  kernel's launch) with ``_refuse_flags``, and ``_round_half_even``, the one rounding rule (``round_like_python`` adds ``round``).
 
 What the device computes differently from numpy is stated in DESIGN.md: box IoU is bit-identical; for OKS the exponent
 argument is bit-identical, ``exp`` and the order of the sum over the landmarks are the device's.
 """
 import ctypes
+import functools
 import json
 import os
 
@@ -175,23 +177,65 @@ def pack_results(packed_gt, results):
     return _pack_dets(packed_gt, kind, img, cat, score, bbox, area, kxy)
 
 
-def round_like_python(values, num_digits):
-    """``[round(float(v), num_digits) for v in values]`` as an array.  Python rounds the exact decimal value correctly;
-    ``np.round`` computes ``rint(v * 10**d) / 10**d`` and differs where the product's own rounding crosses a half.  For
-    ``|v * 10**d| < 2**40`` that product is off by at most 2**-13, so wherever its fraction is further than 1e-3 from 0.5 both
-    pick the same integer n, and both return the double nearest to n / 10**d (a correctly rounded division of two exactly
-    represented integers).  Those elements take ``np.round``; the others (about 0.2 %) take Python's ``round``."""
+ROUND_LIMIT = 2.0 ** 40          # |v * 10**d| the exact rounding holds below (here and in csrc/coco_pack_dets.hip)
+
+
+def _round_half_even_masked(values, num_digits, block=1 << 15):
+    """(rounded float64 array, bool array: the values outside the rounding's domain -- those are returned as they are)"""
     v = np.asarray(values, dtype=np.float64)
-    out = np.round(v, num_digits)
-    if num_digits <= 0:
-        risky = np.ones(v.shape, bool)
+    S = np.float64(10.0 ** num_digits)                              # (exact up to 10**22)
+
+    def split(x):                                                   # Veltkamp: x = hi + lo, 26 bits each
+        t = 134217729.0 * x
+        hi = t - (t - x)
+        return hi, x - hi
+
+    sh, sl = split(S)
+    flat = v.reshape(-1)
+    out, bad = np.empty(flat.shape), np.empty(flat.shape, bool)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for i in range(0, len(flat), block):                        # (blocks whose two dozen temporaries stay in the cache)
+            x = flat[i:i + block]
+            a = np.abs(x)
+            p = a * S
+            bad[i:i + block] = ~(p < ROUND_LIMIT)                   # (a NaN is "bad" too)
+            ah, al = split(a)
+            e = ((ah * sh - p) + ah * sl + al * sh) + al * sl       # Dekker: a * S - p exactly (what fma(a, S, -p) returns)
+            f = np.floor(p)
+            r = p - f
+            odd = np.floor(f * 0.5) * 2.0 != f                      # (exact for an integer f; np.fmod takes 100 ns per element)
+            up = (r > 0.5) | ((r == 0.5) & ((e > 0) | ((e == 0) & odd)))
+            out[i:i + block] = np.where(bad[i:i + block], x, np.copysign((f + up) / S, x))
+    return out.reshape(v.shape), bad.reshape(v.shape)
+
+
+def _round_half_even(values, num_digits):
+    """(rounded float64 array, number of values outside the rounding's domain -- those are returned as they are)"""
+    out, bad = _round_half_even_masked(values, num_digits)
+    return out, int(np.count_nonzero(bad))
+
+
+def round_half_even_restatement(values, num_digits):
+    """``kgdet_coco_order_dets``'s rounding in numpy: bit-equal to ``[round(float(v), num_digits) for v in values]`` for
+    ``1 <= num_digits <= 9`` and finite ``|v * 10**d| < 2**40`` (other values come back unchanged; the packing counts them and
+    raises).  With S = 10**d: p = fl(|v| * S) and the exact residual e = |v| * S - p -- an FMA on the device, a Veltkamp /
+    Dekker product here -- place the exact decimal value against the half: n = floor(p) + 1 where p - floor(p) > 1/2, or
+    == 1/2 with e > 0, or e == 0 and floor(p) odd; else floor(p).  The result is copysign(n / S, v), one correctly rounded
+    division: the double nearest to the decimal Python's ``round`` arrives at, with its sign of zero."""
+    return _round_half_even(values, num_digits)[0]
+
+
+def round_like_python(values, num_digits):
+    """``[round(float(v), num_digits) for v in values]`` as an array: ``round_half_even_restatement`` where that is exact
+    (``1 <= num_digits <= 9``, finite ``|v * 10**d| < 2**40``); the elements outside that domain, and every element for any
+    other ``num_digits``, take Python's ``round`` one by one."""
+    v = np.asarray(values, dtype=np.float64)
+    if 1 <= num_digits <= 9:
+        out, rest = _round_half_even_masked(v, num_digits)
     else:
-        s = v * 10.0 ** num_digits
-        with np.errstate(invalid='ignore'):
-            risky = ~(np.abs(s) < 2.0 ** 40) | (np.abs(np.abs(s - np.floor(s)) - 0.5) <= 1e-3)
-    flat, idx = out.reshape(-1), np.nonzero(risky.reshape(-1))[0]
-    src = v.reshape(-1)
-    for i in idx:
+        out, rest = v.copy(), np.ones(v.shape, bool)
+    flat, src = out.reshape(-1), v.reshape(-1)
+    for i in np.nonzero(rest.reshape(-1))[0]:
         flat[i] = round(float(src[i]), num_digits)
     return flat.reshape(v.shape)
 
@@ -335,51 +379,68 @@ def pack_test_results(packed_gt, dataset, results, num_digits=4, lazy_landmarks=
 # ------------------------------------------------------------------------------------------------
 # pack_test_results for results that stayed on the device (runner.DeviceResults; csrc/coco_pack_dets.hip)
 # ------------------------------------------------------------------------------------------------
-ROUND_LIMIT = 2.0 ** 40          # |v * 10**d| the device rounding is exact below
+def _row_block(rows, dataset, num_labels, num_digits, max_digits):
+    """THE description of a ``runner.DeviceResults.rows`` block (numpy or tensor) -> N, M, W, K, L: float32 [N, M, W = 7 + 3K]
+    -- box, score, label, count, K landmarks -- for a dataset of N samples; image n's count sits in ``rows[n, 0, 6]``, a row is
+    valid when its label lies in [0, L), and L (``num_labels``; None: the dataset's categories) is 1 .. what the dataset names
+    and the order kernel takes.  ``num_digits`` is an int in 1 .. ``max_digits``, the route's ceiling: 9 for the packing (the
+    exact rounding's), ``JSON_MAX_DIGITS`` for the files.  Anything else is a ``ValueError``."""
+    from . import _lib
+    if isinstance(num_digits, bool) or not isinstance(num_digits, (int, np.integer)) or not 1 <= num_digits <= max_digits:
+        raise ValueError('num_digits %r (1 .. %d)' % (num_digits, max_digits))
+    N, M, W = rows.shape
+    K = (W - 7) // 3
+    if W != 7 + 3 * K or K < 1:
+        raise ValueError('rows of %d floats (7 + 3K)' % W)
+    if N != len(dataset):
+        raise ValueError('%d result blocks for a dataset of %d samples' % (N, len(dataset)))
+    L = len(dataset.cat_ids) if num_labels is None else int(num_labels)
+    if not 1 <= L <= min(len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS):
+        raise ValueError('%d labels: the dataset names %d categories, the kernels take up to %d'
+                         % (L, len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS))
+    return N, M, W, K, L
 
 
-def _round_half_even(values, num_digits):
-    """(rounded float64 array, number of values outside the rounding's domain -- those are returned as they are)"""
-    v = np.asarray(values, dtype=np.float64)
-    S = np.float64(10.0 ** num_digits)                              # (exact up to 10**22)
-    with np.errstate(invalid='ignore', over='ignore'):
-        a = np.abs(v)
-        p = a * S
-        bad = ~(p < ROUND_LIMIT)                                    # (a NaN is "bad" too)
-
-        def split(x):                                               # Veltkamp: x = hi + lo, 26 bits each
-            t = 134217729.0 * x
-            hi = t - (t - x)
-            return hi, x - hi
-
-        (ah, al), (sh, sl) = split(a), split(S)
-        e = ((ah * sh - p) + ah * sl + al * sh) + al * sl           # Dekker: a * S - p exactly (what fma(a, S, -p) returns)
-        f = np.floor(p)
-        r = p - f
-        up = (r > 0.5) | ((r == 0.5) & ((e > 0) | ((e == 0) & (np.fmod(f, 2.0) != 0))))
-        out = np.copysign((f + up) / S, v)
-    return np.where(bad, v, out), int(np.count_nonzero(bad))
+def _rows_and_labels(dev_results, device):
+    """(a ``runner.DeviceResults``' rows, on ``device`` when one other than 'cpu' is named; its label count L)"""
+    if dev_results.rows is None:
+        raise ValueError('the device results were released')
+    move = device is not None and str(device) != 'cpu'
+    return (dev_results.rows.to(device) if move else dev_results.rows), int(dev_results.num_classes) - 1
 
 
-def round_half_even_restatement(values, num_digits):
-    """``kgdet_coco_order_dets``'s rounding in numpy: bit-equal to ``[round(float(v), num_digits) for v in values]`` for
-    ``1 <= num_digits <= 9`` and finite ``|v * 10**d| < 2**40`` (other values come back unchanged; the packing counts them and
-    raises).  With S = 10**d: p = fl(|v| * S) and the exact residual e = |v| * S - p -- an FMA on the device, a Veltkamp /
-    Dekker product here -- place the exact decimal value against the half: n = floor(p) + 1 where p - floor(p) > 1/2, or
-    == 1/2 with e > 0, or e == 0 and floor(p) odd; else floor(p).  The result is copysign(n / S, v), one correctly rounded
-    division: the double nearest to the decimal Python's ``round`` arrives at, with its sign of zero."""
-    return _round_half_even(values, num_digits)[0]
+def _image_rows(rows, n, L, num_digits):
+    """THE walk over image ``n`` of a host block, for both numpy restatements: of the first ``count`` rows the valid ones ->
+    (their row indices, their labels, k = a row's place in (label, row) order, float64 [x, y, x2 - x + 1, y2 - y + 1, score] per
+    row, rounded like Python's ``round``, how many of those values lie outside the rounding's domain).  ``ValueError``: a count
+    outside [0, M]."""
+    M, cf = rows.shape[1], rows[n, 0, 6]
+    if not (cf >= 0 and cf < M + 1):
+        raise ValueError('sample %d: count %r outside [0, %d]' % (n, cf, M))
+    r = rows[n, :int(cf)]
+    with np.errstate(invalid='ignore'):
+        src = np.nonzero((r[:, 5] > -1) & (r[:, 5] < L))[0]
+    r = r[src]
+    label = r[:, 5].astype(np.int64)
+    k = np.empty(len(r), np.int64)
+    k[np.argsort(label, kind='mergesort')] = np.arange(len(r))
+    b = r[:, :5].astype(np.float64)
+    xywhs, bad = _round_half_even(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1, b[:, 4]], axis=1),
+                                  num_digits)
+    return src, label, k, xywhs, bad
+
+
+def _refuse_flags(bad_value, bad_layout, M, num_digits, values, layout):
+    """the order kernel's two flag words as ``ValueError``s, in the route's words for what they count"""
+    if bad_value:
+        raise ValueError('%d %s are not finite or reach 2**40 / 10**%d' % (bad_value, values, num_digits))
+    if bad_layout:
+        raise ValueError('%d samples with a count outside [0, %d] %s' % (bad_layout, M, layout))
 
 
 def _pack_tables(packed_gt, dataset, N, L):
     """(img_slot int32 [N]: sample -> index into packed_gt.img_ids, -1 unknown; cat_of_label int32 [L]: label -> index into
-    packed_gt.cat_ids, -1 unknown)"""
-    from . import _lib
-    if N != len(dataset):
-        raise ValueError('%d result blocks for a dataset of %d samples' % (N, len(dataset)))
-    if not 1 <= L <= min(len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS):
-        raise ValueError('%d labels: the dataset names %d categories, the packing kernel takes up to %d'
-                         % (L, len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS))
+    packed_gt.cat_ids, -1 unknown); N and L are ``_row_block``'s"""
     ii, ok_i = _index_of(packed_gt.img_ids, np.asarray(dataset.img_ids[:N], dtype=np.int64).reshape(-1))
     ci, ok_c = _index_of(packed_gt.cat_ids, np.asarray(dataset.cat_ids[:L], dtype=np.int64))
     slot = np.where(ok_i, ii, -1).astype(np.int32)
@@ -408,13 +469,7 @@ def pack_rows_restatement(packed_gt, dataset, rows, num_digits=4, num_labels=Non
     rounding's domain, a count outside [0, M], detections of an image the ground truth does not hold."""
     if not isinstance(rows, np.ndarray):
         rows = rows.cpu().numpy()
-    if not 1 <= num_digits <= 9:
-        raise ValueError('num_digits %r (1 .. 9)' % (num_digits,))
-    N, M, W = rows.shape
-    K = (W - 7) // 3
-    if W != 7 + 3 * K or K < 1:
-        raise ValueError('rows of %d floats (7 + 3K)' % W)
-    L = len(dataset.cat_ids) if num_labels is None else int(num_labels)
+    N, M, W, K, L = _row_block(rows, dataset, num_labels, num_digits, 9)
     pg = packed_gt
     slot, cat_of_label = _pack_tables(pg, dataset, N, L)
     C = len(pg.cat_ids)
@@ -423,34 +478,19 @@ def pack_rows_restatement(packed_gt, dataset, rows, num_digits=4, num_labels=Non
     cnt = np.zeros((2, n_cells), np.int64)
     per_image, img_rows, n_bad = [], np.zeros(N, np.int64), 0
     for n in range(N):
-        cf = rows[n, 0, 6]
-        if not (cf >= 0 and cf < M + 1):
-            raise ValueError('sample %d: count %r outside [0, %d]' % (n, cf, M))
-        r = rows[n, :int(cf)]
-        lf = r[:, 5]
-        with np.errstate(invalid='ignore'):
-            valid = (lf > -1) & (lf < L)
-        r = r[valid]
-        src = np.nonzero(valid)[0]
-        label = r[:, 5].astype(np.int64)
+        src, label, k, xywhs, bad = _image_rows(rows, n, L, num_digits)
         cat = cat_of_label[label].astype(np.int64)
-        img_rows[n] = len(r)
-        if len(r) and slot[n] < 0:
+        img_rows[n] = len(src)
+        if len(src) and slot[n] < 0:
             raise ValueError('Results do not correspond to current coco set')
-        b = r[:, :5].astype(np.float64)
-        xywhs, bad = _round_half_even(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1, b[:, 4]], axis=1),
-                                      num_digits)
         n_bad += bad
-        k = np.empty(len(r), np.int64)
-        k[np.argsort(label, kind='mergesort')] = np.arange(len(r))
-        rank = np.full(len(r), -1, np.int64)
+        rank = np.full(len(src), -1, np.int64)
         for c in np.unique(cat[cat >= 0]):
             sel = np.nonzero(cat == c)[0]
             rank[sel[np.lexsort((k[sel], -xywhs[sel, 4]))]] = np.arange(len(sel))
             cnt[:, slot[n] * C + c] = np.minimum(len(sel), cuts)
         per_image.append((src, cat, k, rank, xywhs))
-    if n_bad:
-        raise ValueError('%d box / score values are not finite or reach 2**40 / 10**%d' % (n_bad, num_digits))
+    _refuse_flags(n_bad, 0, M, num_digits, 'box / score values', '')
     start = np.zeros((2, n_cells + 1), np.int64)
     np.cumsum(cnt, axis=1, out=start[:, 1:])
     img_base = np.cumsum(img_rows) - img_rows
@@ -481,28 +521,47 @@ def pack_device_results(packed_gt, dataset, dev_results, num_digits=4, device=No
     the landmark rows ``kxy32`` of the 'keypoints' Packed are a float32 tensor on the device, which ``_run_device`` slices in
     place of an upload.  ``device``: None = where the rows are.  Rows on the CPU take ``pack_rows_restatement``.
     ``ValueError`` as the restatement's -- ``evaluate_results`` then packs ``to_host()`` on the host."""
-    import torch
-    from . import _lib
-    rows = dev_results.rows
-    if rows is None:
-        raise ValueError('the device results were released')
-    L = int(dev_results.num_classes) - 1
-    if device is not None and str(device) != 'cpu':
-        rows = rows.to(torch.device(device))
+    rows, L = _rows_and_labels(dev_results, device)
     if not rows.is_cuda or rows.shape[0] == 0:
         return pack_rows_restatement(packed_gt, dataset, rows, num_digits, num_labels=L)
-    if not 1 <= num_digits <= 9:
-        raise ValueError('num_digits %r (1 .. 9)' % (num_digits,))
-    rows = rows.contiguous()
-    N, M, W = rows.shape
-    if M > _lib.COCO_ORDER_MAX_ROWS:
-        raise ValueError('%d detections per image: the packing kernel ranks up to %d' % (M, _lib.COCO_ORDER_MAX_ROWS))
+    N, M, W, K, L = _row_block(rows, dataset, L, num_digits, 9)
     slot, cat_of_label = _pack_tables(packed_gt, dataset, N, L)
     C = len(packed_gt.cat_ids)
-    outs, start = _pack_rows_on_device(rows, slot, cat_of_label, C, len(packed_gt.img_ids) * C, num_digits)
+    outs, start = _pack_rows_on_device(rows.contiguous(), slot, cat_of_label, C, len(packed_gt.img_ids) * C, num_digits)
     kxy32 = outs[1].pop('kxy32')
     host = [{f: (t.cpu().numpy() if t is not None else None) for f, t in o.items() if f != 'kxy32'} for o in outs]
     return _packed_pair(host, start.cpu().numpy(), kxy32, num_digits)
+
+
+def _empty_on(dev):
+    import torch
+    return lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _order_rows_on_device(rows, slot_t, col_t, C, n_cells, num_digits, alloc):
+    """THE launch of ``kgdet_coco_order_dets``, for the packing and for the result files: contiguous CUDA ``rows`` [N, M, W],
+    the tables sample -> image slot [N] and label -> column [L] as int32 device tensors, ``C`` columns per image, ``n_cells``
+    cells -> (vals float64 [N, M, 6], info int32 [N, M, 3], img_rows int32 [N], all three from ``alloc(shape, dtype)``; img_base
+    int64 [N], the exclusive scan of img_rows; cnt int32 [2, n_cells], a cell's kept rows under either cut; flags int32 [2]).
+    ``cnt`` and ``flags`` are zeroed here: the kernel writes only the cells of images it knows and adds to the flags.  Nothing
+    is read back.  ``ValueError``: more rows per image than the kernel ranks."""
+    import torch
+    from . import _lib
+    N, M, W = rows.shape
+    if M > _lib.COCO_ORDER_MAX_ROWS:
+        raise ValueError('%d detections per image: the order kernel ranks up to %d' % (M, _lib.COCO_ORDER_MAX_ROWS))
+    dev = rows.device
+    i32, i64, p = ctypes.c_int32, ctypes.c_int64, _lib.ptr
+    with torch.cuda.device(dev):
+        vals, info, img_rows = alloc((N, M, 6), torch.float64), alloc((N, M, 3), torch.int32), alloc((N,), torch.int32)
+        cnt = torch.zeros((2, n_cells), dtype=torch.int32, device=dev)
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().kgdet_coco_order_dets(
+            p(rows), i64(N), i32(M), i32(W), p(slot_t), p(col_t), i32(len(col_t)), i32(C), i64(n_cells), i32(num_digits),
+            i32(MAX_DETS['bbox']), i32(MAX_DETS['keypoints']), p(vals), p(info), p(img_rows), p(cnt[0]), p(cnt[1]), p(flags),
+            _lib.current_stream()), 'kgdet_coco_order_dets')
+        img_base = torch.cumsum(img_rows, dim=0, dtype=torch.int64) - img_rows
+    return vals, info, img_rows, img_base, cnt, flags
 
 
 def _pack_rows_on_device(rows, slot, cat_of_label, C, n_cells, num_digits, alloc=None):
@@ -511,33 +570,18 @@ def _pack_rows_on_device(rows, slot, cat_of_label, C, n_cells, num_digits, alloc
     dtype)``: where the kernels' outputs and intermediates come from (None: ``torch.empty`` on the rows' device)."""
     import torch
     from . import _lib
-    lib = _lib.lib()
     N, M, W = rows.shape
-    L = len(cat_of_label)
     dev = rows.device
-    if alloc is None:
-        def alloc(shape, dtype):
-            return torch.empty(shape, dtype=dtype, device=dev)
+    alloc = _empty_on(dev) if alloc is None else alloc
     i32, i64, p = ctypes.c_int32, ctypes.c_int64, _lib.ptr
-    cut_b, cut_k = MAX_DETS['bbox'], MAX_DETS['keypoints']
     with torch.cuda.device(dev):
-        stream = _lib.current_stream()
         slot_t, col_t = torch.from_numpy(slot).to(dev), torch.from_numpy(cat_of_label).to(dev)
-        vals, info, img_rows = alloc((N, M, 6), torch.float64), alloc((N, M, 3), torch.int32), alloc((N,), torch.int32)
-        cnt = torch.zeros((2, n_cells), dtype=torch.int32, device=dev)
-        flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.kgdet_coco_order_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), p(col_t), i32(L), i32(C), i64(n_cells),
-                                             i32(num_digits), i32(cut_b), i32(cut_k), p(vals), p(info), p(img_rows), p(cnt[0]),
-                                             p(cnt[1]), p(flags), stream), 'kgdet_coco_order_dets')
+        vals, info, img_rows, img_base, cnt, flags = _order_rows_on_device(rows, slot_t, col_t, C, n_cells, num_digits, alloc)
         start = torch.zeros((2, n_cells + 1), dtype=torch.int64, device=dev)
         start[:, 1:] = torch.cumsum(cnt, dim=1, dtype=torch.int64)
-        img_base = torch.cumsum(img_rows, dim=0, dtype=torch.int64) - img_rows
         n_b, n_k, bad_value, bad_layout = torch.cat([start[:, -1], flags.to(torch.int64)]).tolist()     # (the one read-back)
-        if bad_value:
-            raise ValueError('%d box / score values are not finite or reach 2**40 / 10**%d' % (bad_value, num_digits))
-        if bad_layout:
-            raise ValueError('%d samples with a count outside [0, %d] or with detections of an image the ground truth does not '
-                             'hold' % (bad_layout, M))
+        _refuse_flags(bad_value, bad_layout, M, num_digits, 'box / score values',
+                      'or with detections of an image the ground truth does not hold')
         outs, structs = [], []
         for n, lazy in ((n_b, False), (n_k, True)):
             o = dict(cell=alloc((n,), torch.int64), img_idx=alloc((n,), torch.int64), cat_idx=alloc((n,), torch.int64),
@@ -546,10 +590,10 @@ def _pack_rows_on_device(rows, slot, cat_of_label, C, n_cells, num_digits, alloc
                      kxy32=alloc((n, W - 7), torch.float32) if lazy else None)
             outs.append(o)
             structs.append(_lib.CocoPackedDets(n=n, **{f: (o[f].data_ptr() if o[f] is not None else None) for f in o}))
-        _lib.check(lib.kgdet_coco_scatter_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), i32(C), i64(n_cells), p(vals), p(info),
-                                               p(img_base), p(start[0]), p(start[1]), i32(cut_b), i32(cut_k),
-                                               ctypes.byref(structs[0]), ctypes.byref(structs[1]), p(flags), stream),
-                   'kgdet_coco_scatter_dets')
+        _lib.check(_lib.lib().kgdet_coco_scatter_dets(
+            p(rows), i64(N), i32(M), i32(W), p(slot_t), i32(C), i64(n_cells), p(vals), p(info), p(img_base), p(start[0]), p(start[1]),
+            i32(MAX_DETS['bbox']), i32(MAX_DETS['keypoints']), ctypes.byref(structs[0]), ctypes.byref(structs[1]), p(flags),
+            _lib.current_stream()), 'kgdet_coco_scatter_dets')
         if int(flags[1]):
             raise RuntimeError('kgdet_coco_scatter_dets: rows fell outside the packed arrays (counts and scans disagree)')
         return outs, start
@@ -640,6 +684,22 @@ def _run_host(c, want_sim=True):
     return (sim if want_sim else None,) + match_restatement(c, sim)
 
 
+def _is_lazy(packed):
+    """a landmark Packed that carries the float32 rows ``kxy32`` in place of ``kxy`` / ``bbox`` / ``area``"""
+    return packed.kxy is None and getattr(packed, 'kxy32', None) is not None
+
+
+def _upload(dev, a, dtype=None):
+    """an array (cast to ``dtype`` first) or a tensor, contiguous on ``dev``; None stays None"""
+    import torch
+    if a is None:
+        return None
+    if torch.is_tensor(a):                                          # (rows that never left the device: pack_device_results)
+        return a.to(dev).contiguous()
+    a = np.asarray(a)
+    return torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype, copy=False))).to(dev)
+
+
 def _run_device(c, device, want_sim=True, on_device=None):
     """the two launches of csrc/coco_eval.hip for one chunk; the similarity matrix stays on the device between them.  A lazy
     landmark chunk (``c.kxy32``) first runs ``kgdet_coco_pack_landmarks`` on its float32 rows: the two kernels read its
@@ -650,15 +710,7 @@ def _run_device(c, device, want_sim=True, on_device=None):
     from . import _lib
     L = _lib.lib()
     dev = torch.device(device)
-
-    def up(a, dtype=None):
-        if a is None:
-            return None
-        if torch.is_tensor(a):                                      # (rows that never left the device: pack_device_results)
-            return a.to(dev).contiguous()
-        t = torch.from_numpy(np.ascontiguousarray(a if dtype is None else a.astype(dtype, copy=False)))
-        return t.to(dev, non_blocking=False)
-
+    up = functools.partial(_upload, dev)
     A, T = len(c.area_rng), len(c.best0)
     kp = c.iou_type == 'keypoints'
     with torch.cuda.device(dev):
@@ -786,7 +838,7 @@ class DeviceCocoEvaluator(CocoEvaluator):
         common = dict(iou_type=p.iou_type, var=(landmark_meta()['oks_sigmas'] * 2) ** 2,
                       area_rng=np.asarray(p.area_rng, dtype=np.float64).reshape(-1, 2),
                       best0=np.minimum(np.asarray(p.iou_thrs, dtype=np.float64), 1 - 1e-10))
-        lazy = kp and d.kxy is None and getattr(d, 'kxy32', None) is not None      # (rounded by the chunk on the device)
+        lazy = kp and _is_lazy(d)                                   # (rounded by the chunk on the device)
         if lazy:
             common['num_digits'] = d.num_digits
         lo = 0
@@ -813,7 +865,7 @@ class DeviceCocoEvaluator(CocoEvaluator):
         on_cpu = str(self.device) == 'cpu'
         if on_cpu and p.iou_type == 'keypoints':
             materialize(self.dt)                                    # (a lazy Packed: the numpy route)
-        if p.iou_type == 'keypoints' and len(self.dt.score) and self.dt.kxy is None and getattr(self.dt, 'kxy32', None) is None:
+        if p.iou_type == 'keypoints' and len(self.dt.score) and self.dt.kxy is None and not _is_lazy(self.dt):
             raise ValueError('landmark evaluation needs landmark detections')
         dev_acc = self.device_accumulate
         if dev_acc is None:
@@ -829,45 +881,39 @@ class DeviceCocoEvaluator(CocoEvaluator):
                              % (p.max_dets[-1], MAX_DETS[p.iou_type]))
         A, T = len(p.area_rng), len(p.iou_thrs)
         nd, ng = len(self.dt.score), len(self.gt.id)
-        d_match = d_ignore = g_ignore = None
-        sims = []
-        lazy = p.iou_type == 'keypoints' and self.dt.kxy is None and getattr(self.dt, 'kxy32', None) is not None
+        lazy = p.iou_type == 'keypoints' and _is_lazy(self.dt)
         if lazy:
             self.dt.bbox, self.dt.area = np.zeros((nd, 4)), np.zeros(nd)
         size = np.diff(self.dt.start) * np.diff(self.gt.start)
         sim_start = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+        # d_match, d_ignore, g_ignore of the whole dataset, where the chunks' outputs go (np.zeros touches no page by itself)
         if dev_acc:
             import torch
-            dev = torch.device(self.device)
-            on_device = (torch.zeros((nd, A, T), dtype=torch.int32, device=dev), torch.zeros((nd, A, T), dtype=torch.uint8, device=dev),
-                         torch.zeros((ng, A), dtype=torch.uint8, device=dev))
-            for c in self._chunks(CHUNK_DETS[p.iou_type]):
-                sims.append(_run_device(c, self.device, self.keep_similarity, on_device)[0])
-                if lazy:
-                    self.dt.bbox[c.d0:c.d1], self.dt.area[c.d0:c.d1] = c.out_bbox, c.out_area
-            self._out = _DeviceOutputs(on_device, sim_start=sim_start,
-                                       sim=(np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None)
-            return self
-        run = _run_host if on_cpu else (lambda c, want: _run_device(c, self.device, want))
+            out = (torch.zeros((nd, A, T), dtype=torch.int32, device=self.device),
+                   torch.zeros((nd, A, T), dtype=torch.uint8, device=self.device),
+                   torch.zeros((ng, A), dtype=torch.uint8, device=self.device))
+        else:
+            out = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8), np.zeros((ng, A), np.uint8)
+        run = _run_host if on_cpu else functools.partial(_run_device, device=self.device, on_device=out if dev_acc else None)
+        sims = []
         for c in self._chunks(CHUNK_DETS[p.iou_type]):
-            sim, dm, di, gi = run(c, self.keep_similarity)
+            sim, dm, di, gi = run(c, want_sim=self.keep_similarity)
+            sims.append(sim)
             if lazy:
                 self.dt.bbox[c.d0:c.d1], self.dt.area[c.d0:c.d1] = c.out_bbox, c.out_area
+            if dev_acc:
+                continue                                            # (the chunk wrote its slices itself)
             if c.g0:
                 np.add(dm, c.g0, out=dm, where=dm > 0)             # chunk-local -> packed index, in place
             if c.nd == nd and c.ng == ng:
-                d_match, d_ignore, g_ignore = dm, di, gi            # one chunk: the downloaded arrays as they are
+                out = dm, di, gi                                    # one chunk: the downloaded arrays as they are
             else:
-                if d_match is None:
-                    d_match, d_ignore = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8)
-                    g_ignore = np.zeros((ng, A), np.uint8)
-                d_match[c.d0:c.d1], d_ignore[c.d0:c.d1], g_ignore[c.g0:c.g1] = dm, di, gi
-            sims.append(sim)
-        if d_match is None:
-            d_match, d_ignore, g_ignore = np.zeros((nd, A, T), np.int32), np.zeros((nd, A, T), np.uint8), np.zeros((ng, A), np.uint8)
-        self._out = Packed(d_match=d_match, d_ignore=d_ignore.view(bool), g_ignore=g_ignore,
-                           sim=(np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None,
-                           sim_start=sim_start)
+                out[0][c.d0:c.d1], out[1][c.d0:c.d1], out[2][c.g0:c.g1] = dm, di, gi
+        sim = (np.concatenate(sims) if sims else np.zeros(0)) if self.keep_similarity else None
+        if dev_acc:
+            self._out = _DeviceOutputs(out, sim_start=sim_start, sim=sim)
+        else:
+            self._out = Packed(d_match=out[0], d_ignore=out[1].view(bool), g_ignore=out[2], sim=sim, sim_start=sim_start)
         return self
 
     # --- accessors at the level of CocoEvaluator's intermediate results -----------------------------
@@ -924,10 +970,7 @@ class DeviceCocoEvaluator(CocoEvaluator):
         order, cat_cut = category_order(d, K)
         rank = (np.arange(nd) - d.start[d.cell]) if nd else np.zeros(0, np.int64)
         tp_cap = int(np.minimum(np.diff(cat_cut), np.bincount(g.cat_idx, minlength=K)[:K]).max())
-
-        def up(a, dtype):
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(dtype, copy=False))).to(dev)
-
+        up = functools.partial(_upload, dev)
         with torch.cuda.device(dev):
             d_match, d_ignore, g_ignore = self._out.dev
             stream, ptr = _lib.current_stream(), _lib.ptr
@@ -1080,12 +1123,6 @@ def decimals_of_landmarks(values, num_digits):
 
 def _json_tables(dataset, N, L):
     """(image ids int64 [N], category ids int64 [L]) as the records print them; ``ValueError`` for what the kernels do not take"""
-    from . import _lib
-    if N != len(dataset):
-        raise ValueError('%d result blocks for a dataset of %d samples' % (N, len(dataset)))
-    if not 1 <= L <= min(len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS):
-        raise ValueError('%d labels: the dataset names %d categories, the kernels take up to %d'
-                         % (L, len(dataset.cat_ids), _lib.COCO_ORDER_MAX_LABELS))
     tables = []
     for what, ids in (('image', list(dataset.img_ids)[:N]), ('category', list(dataset.cat_ids)[:L])):
         for v in ids:
@@ -1099,41 +1136,26 @@ def _json_records(dataset, rows, num_digits=4, num_labels=None):
     """([bbox record bytes], [keypoints record bytes]) in id order: what ``json_restatement`` joins"""
     if not isinstance(rows, np.ndarray):
         rows = rows.cpu().numpy()
-    if isinstance(num_digits, bool) or not isinstance(num_digits, (int, np.integer)) or not 1 <= num_digits <= JSON_MAX_DIGITS:
-        raise ValueError('num_digits %r (1 .. %d)' % (num_digits, JSON_MAX_DIGITS))
-    N, M, W = rows.shape
-    K = (W - 7) // 3
-    if W != 7 + 3 * K or K < 1:
-        raise ValueError('rows of %d floats (7 + 3K)' % W)
-    L = len(dataset.cat_ids) if num_labels is None else int(num_labels)
+    N, M, W, K, L = _row_block(rows, dataset, num_labels, num_digits, JSON_MAX_DIGITS)
     img_ids, cat_ids = _json_tables(dataset, N, L)
     box_out, kpt_out, n_bad = [], [], 0
     for n in range(N):
-        cf = rows[n, 0, 6]
-        if not (cf >= 0 and cf < M + 1):
-            raise ValueError('sample %d: count %r outside [0, %d]' % (n, cf, M))
-        r = rows[n, :int(cf)]
-        with np.errstate(invalid='ignore'):
-            valid = (r[:, 5] > -1) & (r[:, 5] < L)
-        r = r[valid]
-        r = r[np.argsort(r[:, 5].astype(np.int64), kind='mergesort')]          # label ascending, then row order
-        b = r[:, :5].astype(np.float64)
-        xywhs, bad = _round_half_even(np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1, b[:, 4]], axis=1),
-                                      num_digits)
-        q, neg, bad_k = decimals_of_landmarks(r[:, 7:], num_digits)
+        src, label, k, xywhs, bad = _image_rows(rows, n, L, num_digits)
+        by_k = np.argsort(k)                                        # the records' order: label ascending, then row order
+        src, label, xywhs = src[by_k], label[by_k], xywhs[by_k]
+        q, neg, bad_k = decimals_of_landmarks(rows[n, src, 7:], num_digits)
         n_bad += bad + bad_k
         if bad or bad_k:
             continue
         box_text = format_decimals(*decimals_of_rounded(xywhs, num_digits), num_digits)
         kpt_text = format_decimals(q, neg, num_digits)
-        for i in range(len(r)):
+        for i in range(len(src)):
             x, y, w, h, s = box_text[5 * i:5 * i + 5]
-            tail = '], "score": %s, "category_id": %d}' % (s, cat_ids[int(r[i, 5])])
+            tail = '], "score": %s, "category_id": %d}' % (s, cat_ids[label[i]])
             box_out.append(('{"image_id": %d, "bbox": [%s, %s, %s, %s' % (img_ids[n], x, y, w, h) + tail).encode('ascii'))
             kpt_out.append(('{"image_id": %d, "keypoints": [%s' % (img_ids[n], ', '.join(kpt_text[3 * K * i:3 * K * (i + 1)]))
                             + tail).encode('ascii'))
-    if n_bad:
-        raise ValueError('%d values are not finite or reach 2**40 / 10**%d' % (n_bad, num_digits))
+    _refuse_flags(n_bad, 0, M, num_digits, 'values', '')
     return box_out, kpt_out
 
 
@@ -1213,18 +1235,11 @@ def write_device_results_json(dataset, dev_results, out_file, num_digits=4, chun
     import time
     import torch
     from . import _lib
-    rows = dev_results.rows
-    if rows is None:
-        raise ValueError('the device results were released')
-    if isinstance(num_digits, bool) or not isinstance(num_digits, (int, np.integer)) or not 1 <= num_digits <= JSON_MAX_DIGITS:
-        raise ValueError('num_digits %r (1 .. %d)' % (num_digits, JSON_MAX_DIGITS))
+    rows, L = _rows_and_labels(dev_results, device)
     chunk_bytes = int(chunk_bytes)
     if chunk_bytes < 1:
         raise ValueError('chunk_bytes %r' % (chunk_bytes,))
     files = _json_files(out_file)
-    L = int(dev_results.num_classes) - 1
-    if device is not None and str(device) != 'cpu':
-        rows = rows.to(torch.device(device))
     if timings is None:
         timings = {}
     timings.update(order_measure_s=0.0, kernel_s=0.0, copy_s=0.0, file_s=0.0, bytes=0)
@@ -1241,35 +1256,20 @@ def write_device_results_json(dataset, dev_results, out_file, num_digits=4, chun
             tmp.commit()
         return files
     rows = rows.contiguous()
-    N, M, W = rows.shape
-    K = (W - 7) // 3
-    if W != 7 + 3 * K or not 1 <= K <= _lib.COCO_JSON_MAX_K:
-        raise ValueError('rows of %d floats (7 + 3K, K = 1 .. %d)' % (W, _lib.COCO_JSON_MAX_K))
-    if M > _lib.COCO_ORDER_MAX_ROWS:
-        raise ValueError('%d detections per image: the order kernel ranks up to %d' % (M, _lib.COCO_ORDER_MAX_ROWS))
+    N, M, W, K, L = _row_block(rows, dataset, L, num_digits, JSON_MAX_DIGITS)
+    if K > _lib.COCO_JSON_MAX_K:
+        raise ValueError('%d landmarks: a record of the json kernels holds up to %d' % (K, _lib.COCO_JSON_MAX_K))
     img_ids, cat_ids = _json_tables(dataset, N, L)
-    lib = _lib.lib()
-    dev = rows.device
+    lib, dev, cap, clock = _lib.lib(), rows.device, N * M, time.perf_counter
     i32, i64, p = ctypes.c_int32, ctypes.c_int64, _lib.ptr
-    cap = N * M
-    clock = time.perf_counter
     with torch.cuda.device(dev):
         stream = _lib.current_stream()
         t0 = clock()
-        slot_t = torch.arange(N, dtype=torch.int32, device=dev)
-        col_t = torch.arange(L, dtype=torch.int32, device=dev)
         img_t, cat_t = torch.from_numpy(img_ids).to(dev), torch.from_numpy(cat_ids).to(dev)
-        vals = torch.empty((N, M, 6), dtype=torch.float64, device=dev)
-        info = torch.empty((N, M, 3), dtype=torch.int32, device=dev)
-        img_rows = torch.empty((N,), dtype=torch.int32, device=dev)
-        cnt = torch.empty((2, N * L), dtype=torch.int32, device=dev)
-        flags = torch.zeros(2, dtype=torch.int32, device=dev)
-        _lib.check(lib.kgdet_coco_order_dets(p(rows), i64(N), i32(M), i32(W), p(slot_t), p(col_t), i32(L), i32(L), i64(N * L),
-                                             i32(num_digits), i32(MAX_DETS['bbox']), i32(MAX_DETS['keypoints']), p(vals), p(info),
-                                             p(img_rows), p(cnt[0]), p(cnt[1]), p(flags), stream), 'kgdet_coco_order_dets')
-        del cnt
-        total_rows = torch.cumsum(img_rows, dim=0, dtype=torch.int64)
-        img_base = total_rows - img_rows
+        # identity tables: a sample is its own image slot, a label its own column, so no row is dropped for lack of ground truth
+        vals, info, img_rows, img_base, _, flags = _order_rows_on_device(
+            rows, torch.arange(N, dtype=torch.int32, device=dev), torch.arange(L, dtype=torch.int32, device=dev), L, N * L,
+            num_digits, _empty_on(dev))
         lens = torch.zeros((2, cap), dtype=torch.int32, device=dev)
         rec_src = torch.full((cap,), -1, dtype=torch.int64, device=dev)
         _lib.check(lib.kgdet_coco_json_measure(p(rows), i64(N), i32(M), i32(W), p(vals), p(info), p(img_base), p(img_t), p(cat_t),
@@ -1279,14 +1279,12 @@ def write_device_results_json(dataset, dev_results, out_file, num_digits=4, chun
         offset = torch.zeros((2, cap + 1), dtype=torch.int64, device=dev)
         offset[:, 1:] = torch.cumsum(lens, dim=1, dtype=torch.int64) + 2 * torch.arange(cap, dtype=torch.int64, device=dev)
         del lens, info
-        host = torch.cat([flags.to(torch.int64), total_rows[-1:], offset.reshape(-1)]).cpu().numpy()       # (the one read-back)
+        # the one read-back: both flag words, the number of records, their offsets
+        host = torch.cat([flags.to(torch.int64), img_base[-1:] + img_rows[-1:], offset.reshape(-1)]).cpu().numpy()
         bad_value, bad_layout, R = (int(v) for v in host[:3])
         off = host[3:].reshape(2, cap + 1)
         timings['order_measure_s'] = clock() - t0
-        if bad_value:
-            raise ValueError('%d values are not finite or reach 2**40 / 10**%d' % (bad_value, num_digits))
-        if bad_layout:
-            raise ValueError('%d samples with a count outside [0, %d] (or rows outside the record table)' % (bad_layout, M))
+        _refuse_flags(bad_value, bad_layout, M, num_digits, 'values', '(or rows outside the record table)')
         longest = int(np.diff(off[:, :R + 1], axis=1).max()) if R else 0
         if longest > chunk_bytes:
             raise ValueError('a record of %d bytes does not fit chunk_bytes = %d' % (longest, chunk_bytes))

@@ -141,6 +141,20 @@ def rounding_pool():
     return np.concatenate([rounding_specials(), acc.rounding_values()]).astype(np.float32)
 
 
+def rounding_inputs(d):
+    """the rounding pool plus 200 000 seeded random values inside the rounding's domain |v| * 10**d < 2**40"""
+    from kgdet_amd import evaluation_device as evd
+    rng = np.random.default_rng(2024)
+    lim = min(2000.0, 0.9 * evd.ROUND_LIMIT / 10.0 ** d)
+    pool = rounding_pool().astype(np.float64)
+    coords = rng.uniform(-lim, lim, 60000).astype(np.float32).astype(np.float64)
+    scores = rng.random(60000).astype(np.float32).astype(np.float64)
+    a = rng.uniform(0, min(1e5, lim - 1), 40000).astype(np.float32).astype(np.float64)
+    b = rng.uniform(0, 2 ** -10, 40000).astype(np.float32).astype(np.float64)
+    doubles = rng.uniform(-lim, lim, 40000)                           # (full 53-bit values: the residual is a real product)
+    return np.concatenate([pool, coords, scores, a - b + 1, doubles])
+
+
 def _rounding(rng, K, N, M):
     """x1, y1 and the score of every row come from the rounding pool (the specials first, the rest sampled); x2 - x1 + 1 and
     y2 - y1 + 1 are differences of a large and a tiny float32 whose float64 subtraction has to round"""

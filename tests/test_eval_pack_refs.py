@@ -33,22 +33,9 @@ def assert_same_packed(got, want, what):
     assert same_bits(kxy, wk.kxy32), (what, 'kxy32')
 
 
-def rounding_inputs(d):
-    """the rounding pool of the cases plus 200 000 seeded random values inside the rounding's domain |v| * 10**d < 2**40"""
-    rng = np.random.default_rng(2024)
-    lim = min(2000.0, 0.9 * evd.ROUND_LIMIT / 10.0 ** d)
-    pool = pack.rounding_pool().astype(np.float64)
-    coords = rng.uniform(-lim, lim, 60000).astype(np.float32).astype(np.float64)
-    scores = rng.random(60000).astype(np.float32).astype(np.float64)
-    a = rng.uniform(0, min(1e5, lim - 1), 40000).astype(np.float32).astype(np.float64)
-    b = rng.uniform(0, 2 ** -10, 40000).astype(np.float32).astype(np.float64)
-    doubles = rng.uniform(-lim, lim, 40000)                           # (full 53-bit values: the residual is a real product)
-    return np.concatenate([pool, coords, scores, a - b + 1, doubles])
-
-
 @pytest.mark.parametrize('d', [1, 4, 9])
 def test_rounding_restatement_is_pythons_round(d):
-    v = rounding_inputs(d)
+    v = pack.rounding_inputs(d)
     assert len(v) >= 200000 + len(pack.rounding_pool()) and (np.abs(v) * 10.0 ** d < evd.ROUND_LIMIT).all()
     got = evd.round_half_even_restatement(v, d)
     want = np.array([round(float(x), d) for x in v])
@@ -109,6 +96,9 @@ def test_unknown_image_with_detections_is_refused():
         evd.pack_rows_restatement(pg, other, c.rows, 4)
     with pytest.raises(ValueError):
         evd.pack_test_results(pg, other, c.results, 4, lazy_landmarks=True)
+    for d in (True, 4.0):                                           # (num_digits is an int, as for the result files)
+        with pytest.raises(ValueError):
+            evd.pack_rows_restatement(pg, c.dataset, c.rows, d)
 
 
 @pytest.mark.parametrize('bad', [np.inf, 2e8])

@@ -9,6 +9,7 @@ import pytest
 from kgdet_amd import evaluation as ev
 from kgdet_amd import evaluation_device as evd
 from tests import eval_cases as cases
+from tests import eval_pack_cases as pack
 
 TYPES = ['bbox', 'keypoints']
 
@@ -121,8 +122,13 @@ def test_round_like_python_is_pythons_round():
                         np.array([0.0, -0.0, 2.675, 1e15, -1e15 + 0.3, 5e-5, -5e-5, 1.00005, 0.28515, 1e300, -3.00005])])
     want = np.array([round(float(x), 4) for x in v])
     assert np.array_equal(evd.round_like_python(v, 4), want)
-    assert (np.round(v, 4) != want).any()                  # (the shortcut without the repair would be wrong here)
+    assert (np.round(v, 4) != want).any()                  # (np.round alone is wrong on these inputs)
     assert np.array_equal(evd.round_like_python(v[:100], 0), np.array([round(float(x), 0) for x in v[:100]]))
+    outside = np.array([1e15, -1e15 + 0.3, 1e300, 2.0 ** 40 / 1e4, np.nan, np.inf, -np.inf])
+    for d, values in [(d, np.concatenate([pack.rounding_inputs(d), outside])) for d in (1, 4, 9)] + [(d, np.concatenate([v, outside])) for d in (0, -1, 10)]:
+        got, want = evd.round_like_python(values, d), np.array([round(float(x), d) for x in values])
+        bad = np.nonzero((got.view(np.int64) != want.view(np.int64)) & ~(np.isnan(got) & np.isnan(want)))[0]
+        assert len(bad) == 0, (d, values[bad[:5]], got[bad[:5]], want[bad[:5]])      # (bit patterns: the sign of a zero counts)
 
 
 def test_pack_test_results_equals_the_route_through_files(tmp_path):

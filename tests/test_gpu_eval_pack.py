@@ -190,6 +190,9 @@ def test_argument_checks_refuse_before_any_launch():
                scatter(start_b=null), scatter(flags=null), scatter(out_b=ctypes.POINTER(_lib.CocoPackedDets)())]
     assert refused == [_lib.KGDET_E_SHAPE] * len(refused), refused
     assert order(N=0, rows=null) == 0 and scatter(N=0, rows=null) == 0            # (N == 0: a no-op)
+    for d in (True, 4.0):                                                         # (num_digits is an int: the wrapper's refusal)
+        with pytest.raises(ValueError):
+            evd.pack_device_results(pg, c.dataset, DeviceResults(t['rows'], c.n_labels + 1), num_digits=d)
     torch.cuda.synchronize()
     alloc.check()
     for buf, n in alloc.blocks:                                                   # nothing was launched: the fill is intact

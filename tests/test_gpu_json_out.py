@@ -19,9 +19,11 @@ from kgdet_amd import evaluation as ev
 from kgdet_amd import evaluation_device as evd
 from kgdet_amd.checkpoint import save_checkpoint
 from kgdet_amd.runner import DeviceResults, single_gpu_test
+from tests import eval_pack_cases as pack
 from tests import json_cases as jc
 from tests import loader_cases as lc
 from tests.golden import demo_cases
+from tests.test_eval_pack_refs import assert_same_packed
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -156,9 +158,13 @@ def test_flag_word_counts_landmark_values_outside_the_domain_once_each():
     assert Measured(c, rows).flags.cpu().numpy().tolist() == [3, 0]
 
 
-def test_argument_checks_refuse_before_any_launch():
+def test_argument_checks_refuse_before_any_launch(tmp_path):
     c = jc.case('k1')
     m = Measured(c)
+    for d in (True, 4.0):                                           # (num_digits is an int: the wrapper's refusal)
+        with pytest.raises(ValueError):
+            evd.write_device_results_json(c.dataset, DeviceResults(m.rows, c.n_labels + 1), str(tmp_path / 'dev'), num_digits=d)
+    assert os.listdir(str(tmp_path)) == []
     null = vp(0)
     want = _want(c)[1][2]
     refused = [m.write(1, 0, m.R, override=kw) for kw in (
@@ -261,6 +267,24 @@ def test_what_the_device_route_refuses_goes_down_the_host_route_with_one_warning
     dev.release()
     with pytest.raises(ValueError):
         evd.write_device_results_json(c.dataset, dev, str(tmp_path / 'gone'))
+
+
+def test_packing_and_writing_in_turn_on_the_same_rows(tmp_path):
+    """``kgdet_coco_order_dets`` has one launch site, which serves the packing (the ground truth's tables) and the files
+    (identity tables) -- here in turn, in one process, on the same rows: each result against its restatement"""
+    c = jc.case('k1')
+    data = pack.Dataset(ev.CocoIndex(pack.ground_truth(jc.IMG_IDS, 0)), c.dataset.img_ids, c.dataset.cat_ids)
+    pg = pack.packed_gt(pack.Case(dataset=data, K=c.K))
+    want_packed = evd.pack_rows_restatement(pg, data, c.rows, 4, num_labels=c.n_labels)
+    want_files = evd.json_restatement(data, c.rows, 4, num_labels=c.n_labels)
+    assert 0 < len(want_packed['bbox'].score) < int(np.nansum(c.rows[:, 0, 6]))     # (some rows have no ground-truth category)
+    dev = DeviceResults(torch.from_numpy(c.rows).cuda(), c.n_labels + 1)
+    assert_same_packed(evd.pack_device_results(pg, data, dev), want_packed, 'before the files')
+    files = evd.write_device_results_json(data, dev, str(tmp_path / 'dev'))
+    for kind, want in zip(KINDS, want_files):
+        with open(files[kind], 'rb') as f:
+            assert f.read() == want, kind
+    assert_same_packed(evd.pack_device_results(pg, data, dev), want_packed, 'after the files')
 
 
 # ------------------------------------------------------------------------------------------------

@@ -86,7 +86,7 @@ def test_an_empty_set_gives_empty_lists(tmp_path):
 
 def test_what_the_restatement_refuses():
     c = jc.case('k1')
-    for d in (0, 5, -1, 2.0, True):
+    for d in (0, 5, -1, 2.0, 4.0, True):
         with pytest.raises(ValueError):
             evd.json_restatement(c.dataset, c.rows, d)
     for value in jc.OUTSIDE:
