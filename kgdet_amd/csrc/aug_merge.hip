@@ -2,11 +2,13 @@
 // decoded candidates mapped back to the original image frame and concatenated, in one launch per image.
 //
 // Per augmentation a (img_shape width w, scalar scale_factor s), row by row in augmentation order:
-//   flip:  x1' = (w - x2) - 1, x2' = (w - x1) - 1 (y unchanged); each landmark x' = (w - x) - 1 and the landmark of slot
-//          perm[k] lands in slot k (perm = flip_indices[0::2] // 2, an involution, so this IS "slot k moves to perm[k]")
+//   flip:  x1' = (w - x2) - 1, x2' = (w - x1) - 1 (y unchanged); each landmark x' = (w - x) - 1 and the landmarks are
+//          GATHERED: out slot k takes input slot perm[k] (perm = flip_indices[0::2] // 2; the Python callers only pass
+//          involutions, for which a scatter would give the same -- the C ABI takes any permutation and gathers)
 //   then:  box coordinates and landmark x / y times (1 / s) -- torch on the GPU divides by a python float as x * (1 / s)
-//          with the reciprocal taken in double and rounded to fp32 once (the detector's restatement divides that way);
-//          visibility and scores are copied.
+//          with the reciprocal taken in double and rounded to fp32 once, so the detector's restatement gives these bits on
+//          GPU tensors; on CPU tensors it divides truly and may differ in the last bit (both within 2 * 2^-24 |x / s| of
+//          the quotient); visibility and scores are copied bit for bit.
 // Contraction is off: every expression is rounded in the order written, as torch evaluates it op by op.
 //
 // Work split: one workgroup per tile of kTileRows rows of ONE augmentation.  The tile's landmark rows (K * 3 floats each,

@@ -324,9 +324,16 @@ def merge_aug_results_kp(aug_bboxes, aug_scores, aug_kpts, img_metas):
     mmdet/core/bbox/transforms.py:71-103, with the landmarks carried through); any device.
 
     Per augmentation (meta: ``img_shape``, scalar ``scale_factor`` s, ``flip``, ``flip_indices``): a flip maps
-    x1' = (w - x2) - 1, x2' = (w - x1) - 1 and every landmark x' = (w - x) - 1 with w = img_shape[1], and moves the landmark
-    in slot k to slot perm[k], perm = flip_indices[0::2] // 2; then box coordinates and landmark x, y are divided by s.
-    Visibility and scores are unchanged.  The rows are concatenated in augmentation order.
+    x1' = (w - x2) - 1, x2' = (w - x1) - 1 and every landmark x' = (w - x) - 1 with w = img_shape[1], and GATHERS the
+    landmarks: out slot k takes the landmark of input slot perm[k], perm = flip_indices[0::2] // 2 (``flip_perm`` only lets
+    involutions through, for which that is also "slot k moves to slot perm[k]"); then box coordinates and landmark x, y are
+    divided by s.  Visibility and scores are unchanged.  The rows are concatenated in augmentation order.
+
+    The division is torch's: on a GPU ``x / s`` is ``x * float32(1 / s)`` (the reciprocal taken in double, rounded once), on
+    the CPU a true division.  The two agree bit for bit where 1 / s is a float32 (s = 0.5, 1, 2, ...) and otherwise in all but
+    the last bit: both lie within ``2 U |x / s|`` (+ the two roundings of a flip), U = 2^-24, of the exact quotient
+    (tests/aug_merge_cases.py counts the bound; at s = 1.666 a third of the coordinates differ in that bit).  The kernel
+    (``postprocess.aug_merge_kp``) is bit-identical to this function on GPU tensors, and within that bound of it on CPU tensors.
     aug_bboxes [n,4], aug_scores [n,1+C], aug_kpts [n,K,3] per augmentation -> (bboxes [T,4], scores [T,1+C], kpts [T,K,3])."""
     from .postprocess import aug_scale_factor, flip_perm
     out_b, out_k = [], []

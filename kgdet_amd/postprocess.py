@@ -214,8 +214,12 @@ def aug_scale_factor(meta):
 def aug_merge_kp(aug_bboxes, aug_scores, aug_kpts, img_metas):
     """``detector.merge_aug_results_kp`` on the GPU in ONE launch (csrc/aug_merge.hip ``kgdet_aug_merge``): A <= 16
     augmentations' candidates -- bboxes [n,4], scores [n,1+C], kpts [n,K,3] per augmentation, in its resized frame --
-    mapped back to the original frame (flip undone, divided by the scale factor) and concatenated in augmentation order.
-    Returns (bboxes [T,4], scores [T,1+C], kpts [T,K,3]); bit-identical to the restatement on the same device."""
+    mapped back to the original frame (flip undone, landmarks gathered: out slot k takes input slot perm[k]; coordinates
+    times ``float32(1 / s)``) and concatenated in augmentation order.  kpts may also be [n,3K]; candidates that are row slices
+    of larger tensors are taken in place (boxes, scores and landmark rows need 4-byte alignment only).
+    Returns (bboxes [T,4], scores [T,1+C], kpts [T,K,3]): bit-identical to the restatement evaluated on GPU tensors, where
+    torch divides by a python float the same way; the restatement on CPU tensors divides truly and differs in the last bit of
+    some coordinates, within the bound counted in tests/aug_merge_cases.py."""
     import ctypes
     from . import _lib
     A = len(aug_bboxes)
