@@ -1055,6 +1055,35 @@ int kgdet_draw_detections(const uint8_t *src, int64_t src_bytes, uint8_t *dst, i
                           int32_t name_total, const int32_t *ranges, const uint8_t *glyphs, float score_thr, int32_t thickness,
                           int32_t radius, int32_t contour, int32_t line_width, int32_t font_scale, int32_t kpt_color,
                           void *stream);
+/* Baseline JPEG files of RGB pictures in device memory (csrc/jpeg.hip; kgdet_amd/jpeg.py: DeviceJpegEncoder), byte for byte
+ * the file jpeg.jpeg_restatement defines: JFIF, SOF0, Y / Cb / Cr sampled 2x2 / 1x1 / 1x1, one interleaved scan, the Annex K.1
+ * quantisation tables scaled by the IJG rule for `quality`, the Annex K.3 Huffman tables, integer colour conversion, DCT and
+ * quantisation with the roundings stated there.  One call takes n <= KGDET_JPEG_MAX_IMAGES images of different sizes out of
+ * one flat uint8 buffer (RGB, H x W x 3, rows packed): table is a HOST array int64 [n][4] = (source offset, file offset, H, W),
+ * the layout of kgdet_draw_detections' table, read and checked before any launch -- the drawer's destination buffer and
+ * table serve as they are.
+ * kgdet_jpeg_encode: transform (one wave per MCU) -> int16 coefficients; measure (one wave per MCU, lane = zigzag place) ->
+ * bits per MCU; a scan per image; pack (a workgroup per KGDET_JPEG_RANGE_BYTES bytes of the unstuffed stream, boundary MCUs
+ * coded by both neighbours, bits ORed into LDS) -> the stream and the 0xFF count of each range; a scan of those counts.  All
+ * of it stays in `workspace` (16-byte aligned, kgdet_jpeg_workspace_bytes(table, n) bytes: about 2 KiB per MCU, the stream at
+ * its worst case; 0 for a table that would be refused); lengths int64 [n] (device) = the bytes of each file.  Column 1 of the
+ * table is not read.  The caller reads `lengths` back -- the one read-back -- and sizes the output.
+ * kgdet_jpeg_write: the same table, n, quality and workspace; file i goes to out + table[i][1] when lengths[i] <= capacity[i]
+ * (HOST int64 [n]) and status[i] (device int32 [n]) becomes 0; else NOTHING of it is written and status[i] becomes 1.  Nothing
+ * outside [out + table[i][1], + lengths[i]) is written.  The bytes do not depend on launch geometry or schedule (integers
+ * only; LDS integer OR, no global atomics).
+ * Refused before any launch with nothing written (KGDET_E_SHAPE): n outside [0, KGDET_JPEG_MAX_IMAGES], quality outside [1,
+ * 100], H or W outside [1, 8192], an image outside the source buffer, a file offset / capacity outside the output buffer,
+ * capacities of two images that overlap, overlapping source / workspace / lengths (encode) or output / workspace / status
+ * (write), a workspace that is not 16-byte aligned, a negative size, a null pointer where data is required; a workspace that is
+ * too small is KGDET_E_WORKSPACE.  n == 0 is a no-op. */
+#define KGDET_JPEG_MAX_IMAGES 32
+#define KGDET_JPEG_RANGE_BYTES 4096
+size_t kgdet_jpeg_workspace_bytes(const int64_t *table, int32_t n);
+int kgdet_jpeg_encode(const uint8_t *src, int64_t src_bytes, const int64_t *table, int32_t n, int32_t quality, void *workspace,
+                      size_t workspace_bytes, int64_t *lengths, void *stream);
+int kgdet_jpeg_write(const int64_t *table, int32_t n, int32_t quality, const void *workspace, size_t workspace_bytes,
+                     const int64_t *capacity, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

@@ -49,6 +49,7 @@ COCO_ORDER_MAX_ROWS = 1024    # KGDET_COCO_ORDER_MAX_ROWS: detections per image 
 COCO_ORDER_MAX_LABELS = 64    # KGDET_COCO_ORDER_MAX_LABELS
 COCO_JSON_MAX_K = 1024        # KGDET_COCO_JSON_MAX_K: landmarks of a record kgdet_coco_json_write assembles in LDS
 DRAW_MAX_IMAGES, DRAW_MAX_ROWS, DRAW_MAX_K, DRAW_MAX_LABELS = 32, 1024, 1024, 64    # KGDET_DRAW_MAX_*: kgdet_draw_detections
+JPEG_MAX_IMAGES, JPEG_RANGE_BYTES = 32, 4096    # KGDET_JPEG_*: kgdet_jpeg_encode (jpeg.py carries the same numbers)
 
 
 class CocoPackedDets(ctypes.Structure):
@@ -137,6 +138,13 @@ def lib():
             L.kgdet_draw_detections.restype = ctypes.c_int
             L.kgdet_draw_detections.argtypes = ([vp, i64, vp, i64, vp, vp, i32, vp, i64, i32, i32, vp, i32, vp, vp, i32, vp, vp,
                                                  ctypes.c_float] + [i32] * 6 + [vp])
+        if hasattr(L, 'kgdet_jpeg_encode'):          # jpeg.py: host tables, int64 and size_t sizes among the arguments
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_jpeg_workspace_bytes.restype = ctypes.c_size_t
+            L.kgdet_jpeg_workspace_bytes.argtypes = [vp, i32]
+            L.kgdet_jpeg_encode.restype = L.kgdet_jpeg_write.restype = ctypes.c_int
+            L.kgdet_jpeg_encode.argtypes = [vp, i64, vp, i32, i32, vp, ctypes.c_size_t, vp, vp]
+            L.kgdet_jpeg_write.argtypes = [vp, i32, i32, vp, ctypes.c_size_t, vp, vp, i64, vp, vp]
         _lib = L
     return _lib
 

@@ -334,10 +334,16 @@ class _Show(object):
     ``dataset.load_image`` -- are drawn in one launch (``visualize.DeviceDrawer``) from the group's rows: the slice of the
     sink's device tensor with ``device_results``, else the results just computed, packed and uploaded.  Only the finished
     pictures come back to the host, where ``visualize.PictureWriter``'s threads encode them into
-    ``show_dir/<basename of the image file><ext>``."""
+    ``show_dir/<basename of the image file><ext>``.  ``encoder='device'``: the drawn group stays where it is, is encoded there
+    (``jpeg.DeviceJpegEncoder``, quality 90), only the files' bytes come down and the threads only write them."""
 
-    def __init__(self, model, dataset, show_dir, score_thr, ext, workers):
+    def __init__(self, model, dataset, show_dir, score_thr, ext, workers, encoder='host'):
         from .visualize import PictureWriter
+        if encoder not in ('host', 'device'):
+            raise ValueError("show_encoder is 'host' or 'device', got %r" % (encoder,))
+        if encoder == 'device' and ext.lower() not in ('.jpg', '.jpeg'):
+            raise ValueError("show_encoder='device' writes JPEG files: show_ext is .jpg, got %r" % (ext,))
+        self.encoder = None
         target = model.module if hasattr(model, 'module') else model
         self.dataset, self.score_thr = dataset, score_thr
         self.device = next(target.parameters()).device
@@ -346,6 +352,9 @@ class _Show(object):
         self.names = names if len(names) == L else ['%d' % c for c in range(L)]
         self.drawers = {}                     # by K: an image without detections comes as rows of one landmark
         self.writer = PictureWriter(show_dir, workers, ext)
+        if encoder == 'device':
+            from .jpeg import DeviceJpegEncoder
+            self.encoder = DeviceJpegEncoder(90, device=self.device)
 
     def name(self, idx):
         filename = self.dataset.img_infos[idx].get('filename')
@@ -361,6 +370,10 @@ class _Show(object):
                                            device=self.device)
         if raws is None:
             raws = [self.dataset.load_image(i) for i in idxs]
+        if self.encoder is not None:
+            for idx, data in zip(idxs, self.encoder(self.drawers[K](raws, block, to_host=False))):
+                self.writer.put_bytes(data, self.name(idx))
+            return
         for idx, picture in zip(idxs, self.drawers[K](raws, block, to_host=True)):
             self.writer.put(picture, self.name(idx))
 
@@ -369,7 +382,7 @@ class _Show(object):
 
 
 def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False,
-                    device_results=False, workers=0, show_dir=None, show_score_thr=0.3, show_ext='.jpg'):
+                    device_results=False, workers=0, show_dir=None, show_score_thr=0.3, show_ext='.jpg', show_encoder='host'):
     """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
     resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
     used then) instead of ``dataset[i]``'s host transform; same result format and order.  ``device_results``: the
@@ -380,12 +393,15 @@ def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1
     image is drawn at its original size with the detections above ``show_score_thr`` (``_Show``) and written to
     ``show_dir/<basename of the image file><show_ext>`` ('.jpg' at quality 90, or '.png') by ``workers`` threads, at least 1, at
     most 16; what the call returns does not change.  It needs ``rescale=True`` (``ValueError`` before the run); a writer's
-    exception is re-raised, and the threads are gone when the call returns or raises."""
+    exception is re-raised, and the threads are gone when the call returns or raises.  ``show_encoder``: 'host' -- the drawn
+    pictures are downloaded and the threads encode them (PIL); 'device' -- they are encoded on the GPU (``jpeg.py``: baseline
+    JPEG, quality 90, the bytes of ``jpeg.jpeg_restatement``, not PIL's), only the files come down and the threads only write;
+    it takes ``show_ext`` '.jpg' / '.jpeg' (``ValueError`` before the run)."""
     if show_dir is None:
         return _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, None)
     if not rescale:
         raise ValueError('show_dir draws on the original images: it needs rescale=True')
-    show = _Show(model, dataset, show_dir, show_score_thr, show_ext, workers)
+    show = _Show(model, dataset, show_dir, show_score_thr, show_ext, workers, show_encoder)
     failed = True
     try:
         out = _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show)

@@ -402,8 +402,9 @@ def show_result(img, result, class_names, score_thr=0.3, wait_time=0, show=False
     what ``inference_detector`` returns for it.  Drawn by ``kgdet_draw_detections`` when a GPU and the library are there,
     else by ``draw_restatement`` -- the same bits.  ``style``: ``thickness``, ``radius``, ``contour``, ``line_width``,
     ``font_scale``, ``kpt_color``, ``colors``, ``landmark_ranges`` (default: DeepFashion2's for its 13 classes and 294
-    landmarks).  Returns the array when ``out_file`` is None, else writes that file (PIL, by its extension).  ``show=True``
-    raises: there is no window system (``wait_time`` is the reference's and unused)."""
+    landmarks).  Returns the array when ``out_file`` is None, else writes that file (PIL, by its extension -- a ``.jpg`` too:
+    PIL's encoder at quality 90; for the bytes of the GPU encoder pass the returned array to ``jpeg.encode_jpeg``).
+    ``show=True`` raises: there is no window system (``wait_time`` is the reference's and unused)."""
     if show:
         raise NotImplementedError('show=True needs a window system; pass out_file or take the returned array')
     if isinstance(img, str):
@@ -426,7 +427,8 @@ def show_result(img, result, class_names, score_thr=0.3, wait_time=0, show=False
 
 class PictureWriter(object):
     """finished pictures -> files of ``show_dir``, encoded by a bounded pool of ``workers`` threads (at least 1, at most 16):
-    ``put`` blocks while 2 x workers pictures wait, and re-raises a writer's exception; ``close()`` ends the threads -- after a
+    ``put`` (an array, encoded by the thread) and ``put_bytes`` (a file's bytes, only written by it) block while 2 x workers
+    pictures wait, and re-raise a writer's exception; ``close()`` ends the threads -- after a
     failure (``failed=True``) without waiting for queued pictures, otherwise after the last one, re-raising what it met."""
 
     def __init__(self, show_dir, workers=1, ext='.jpg'):
@@ -442,10 +444,20 @@ class PictureWriter(object):
     def _write(self, array, name):
         save_image(array, os.path.join(self.dir, name + self.ext), self.ext)
 
+    def _write_bytes(self, data, name):
+        with open(os.path.join(self.dir, name + self.ext), 'wb') as f:
+            f.write(data)
+
     def put(self, array, name):
         while len(self.pending) >= 2 * self.workers:
             self.pending.popleft().result()
         self.pending.append(self.pool.submit(self._write, array, name))
+
+    def put_bytes(self, data, name):
+        """a finished file (``jpeg.DeviceJpegEncoder``'s bytes): the thread only writes it; same queue and bounds as ``put``"""
+        while len(self.pending) >= 2 * self.workers:
+            self.pending.popleft().result()
+        self.pending.append(self.pool.submit(self._write_bytes, data, name))
 
     def close(self, failed=False):
         try:

@@ -2,7 +2,7 @@
 
     python tools/test.py CONFIG CHECKPOINT [--json_out P] [--eval bbox keypoints] [--workers N] [--imgs-per-gpu N]
                                            [--device-preprocess] [--device-results] [--out FILE.pkl]
-                                           [--show-dir DIR] [--show-score-thr T]
+                                           [--show-dir DIR] [--show-score-thr T] [--show-encoder {host,device}]
 
 ``cfg.data.test`` goes through ``runner.single_gpu_test``: ``--workers`` threads decode and prepare the upcoming images
 (default ``cfg.data.workers_per_gpu``), ``--imgs-per-gpu`` images of one shape share a forward pass, ``--device-preprocess``
@@ -13,7 +13,9 @@ those files with ``coco_eval``; without it ``--eval`` evaluates the results wher
 ``--out FILE.pkl`` is the reference's pickle of the result list (with ``--device-results``: of ``to_host()``).  ``--show-dir DIR``
 (the reference's ``--show``, into files): every image with its detections above ``--show-score-thr`` and their landmarks, drawn
 on the GPU a group at a time (``kgdet_draw_detections``) and encoded to ``DIR/<image file name>.jpg`` by the ``--workers``
-threads.  A ``--launcher`` other than ``none`` is refused: the multi-rank launch is not part of this tool."""
+threads; with ``--show-encoder device`` the pictures are encoded on the GPU as well (``kgdet_jpeg_encode``: baseline JPEG at
+quality 90, other bytes than PIL's) and the threads only write the files.  A ``--launcher`` other than ``none`` is refused:
+the multi-rank launch is not part of this tool."""
 import argparse
 import os
 import sys
@@ -35,6 +37,8 @@ def parse_args(argv=None):
     parser.add_argument('--out', help='output result file (a pickle of the result list)')
     parser.add_argument('--show-dir', help='directory the drawn images are written to')
     parser.add_argument('--show-score-thr', type=float, default=0.3, help='score threshold of the drawn detections')
+    parser.add_argument('--show-encoder', choices=['host', 'device'], default='host',
+                        help='where the drawn images become JPEG files: PIL in the writer threads, or kernels on the GPU')
     parser.add_argument('--launcher', default='none', help='job launcher (only "none")')
     return parser.parse_args(argv)
 
@@ -63,7 +67,7 @@ def main(argv=None):
     results = single_gpu_test(model, dataset, rescale=True, to_device=lambda t: t.cuda(non_blocking=True),
                               imgs_per_gpu=args.imgs_per_gpu, device_preprocess=args.device_preprocess,
                               device_results=args.device_results, workers=min(workers, 16), show_dir=args.show_dir,
-                              show_score_thr=args.show_score_thr)
+                              show_score_thr=args.show_score_thr, show_encoder=args.show_encoder)
     if args.out:
         import pickle
         print('writing results to {}'.format(args.out))
