@@ -1084,6 +1084,68 @@ int kgdet_jpeg_encode(const uint8_t *src, int64_t src_bytes, const int64_t *tabl
                       size_t workspace_bytes, int64_t *lengths, void *stream);
 int kgdet_jpeg_write(const int64_t *table, int32_t n, int32_t quality, const void *workspace, size_t workspace_bytes,
                      const int64_t *capacity, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream);
+/* Baseline JPEG files -> RGB pictures in device memory (csrc/jpeg_decode.hip; kgdet_amd/jpeg.py: DeviceJpegDecoder), bit for
+ * bit the picture jpeg.decode_restatement defines (libjpeg's islow inverse DCT, fancy chroma upsampling and colour conversion
+ * in integers), which is held to PIL's decoder.  The host parses the header (jpeg.parse_header) and uploads the files' bytes;
+ * `src` is one flat device buffer that holds, per image, the scan's bytes (from the first entropy byte up to at least the
+ * marker that ends it) and a table block of KGDET_JPEG_DECODE_TABLE_BYTES bytes:
+ *   [0, 192)    quantisation tables of components 0, 1, 2, uint8, natural (row-major) order
+ *   [192, 224)  BITS of the DC Huffman tables 0 and 1      [224, 256)  their values, 16 each
+ *   [256, 288)  BITS of the AC Huffman tables 0 and 1      [288, 800)  their values, 256 each
+ *   [800, 803)  DC table of components 0, 1, 2             [803, 806)  AC table of components 0, 1, 2
+ * The workspace begins with uint32 [32] stream lengths and uint32 [32] rounds the fixpoint took (the most of an image's chunks).
+ * `jobs` is a HOST array [n], read and checked before any launch.  mode: one component (its scan is not padded to an MCU), or
+ * three components Y / Cb / Cr sampled 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1.  out + dst_offset receives H x W x 3 RGB bytes,
+ * rows packed.  status (device int32 [n]) becomes 0, or non-zero for a scan the decoder refuses: KGDET_JPEG_DECODE_NO_MARKER
+ * (no marker before the buffer ends), _NOT_EOI (another marker than EOI ends the scan), _BAD_SCAN (an unmatched code, a zigzag
+ * index past 63, a DC category above 11 or an AC category above 10, a block count other than the frame's, an end that is not
+ * within the last byte of the stream).  The output region of such an image may hold anything; nothing outside the image's own
+ * regions is written.  The table block's CONTENT is not checked (it lies on the device): every index made from it is clamped.
+ * Kernels, all on `stream`, no read-back, a workgroup per image in the first two:
+ *   unstuff  the scan ends at the first 0xFF that a byte other than 0x00 follows; a counted scan and a compaction remove the
+ *            0xFF 0x00 stuffing.
+ *   huffman  self-synchronising parallel decoding.  The stream is cut into subsequences of KGDET_JPEG_DECODE_SUBSEQ_BITS bits; a
+ *            lane decodes the symbols that START in its subsequence from an entry state (bit position, block slot of the MCU,
+ *            zigzag index) and records its exit state and the blocks it completed.  The workgroup takes
+ *            KGDET_JPEG_DECODE_CHUNK_LANES subsequences at a time: the first lane's entry is the true state, the others start
+ *            cold, and exit[i] -> entry[i + 1] is iterated with barriers and a workgroup-wide vote until nothing changes (round
+ *            k fixes lane k at the latest: at most as many rounds as lanes, whatever the picture; speculative lanes write
+ *            states only; a lane whose predecessor's parse was invalid keeps its cold start).  Then an exclusive scan of the block counts, a second decode of every subsequence from its true
+ *            state that stores the non-zero coefficients (int16, natural order, every index checked), and at the end the
+ *            inclusive scan of the DC differences per component.
+ *   idct     a thread per block: dequantise, inverse DCT -> sample planes.      colour  upsample, convert, 16-byte stores at
+ *            destination alignment with byte heads and tails.
+ * Integers only: the picture does not depend on launch geometry or schedule.  No global atomics.
+ * Refused before any launch with nothing written (KGDET_E_SHAPE): n outside [0, KGDET_JPEG_DECODE_MAX_IMAGES], H or W outside
+ * [1, 8192], an unknown mode, scan_bytes outside [2, 2^28], a scan or table block outside `src`, a picture outside `out`,
+ * pictures that overlap, overlapping src / workspace / out / status, a workspace that is not 16-byte aligned or smaller than
+ * kgdet_jpeg_decode_workspace_bytes(jobs, n) (0 for jobs that would be refused), a negative size, a null pointer where data is
+ * required.  n == 0 is a no-op. */
+#define KGDET_JPEG_DECODE_MAX_IMAGES 32
+#define KGDET_JPEG_DECODE_SUBSEQ_BITS 512
+#define KGDET_JPEG_DECODE_CHUNK_LANES 1024
+#define KGDET_JPEG_DECODE_TABLE_BYTES 1024
+#define KGDET_JPEG_DECODE_GREY 0
+#define KGDET_JPEG_DECODE_444 1
+#define KGDET_JPEG_DECODE_420 2
+#define KGDET_JPEG_DECODE_NO_MARKER 1
+#define KGDET_JPEG_DECODE_NOT_EOI 2
+#define KGDET_JPEG_DECODE_BAD_SCAN 3
+#define KGDET_JPEG_DECODE_STOPPED (-1) /* kgdet_jpeg_decode_stages with stages < 4: no picture */
+typedef struct kgdet_jpeg_decode_job {
+  int64_t scan_offset, scan_bytes; /* inside src */
+  int64_t tables_offset;           /* inside src */
+  int64_t dst_offset;              /* inside out */
+  int32_t H, W, mode, reserved;
+} kgdet_jpeg_decode_job;
+size_t kgdet_jpeg_decode_workspace_bytes(const kgdet_jpeg_decode_job *jobs, int32_t n);
+int kgdet_jpeg_decode(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
+                      size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream);
+/* For timing only (tools/time_jpeg_decode.py): kgdet_jpeg_decode cut short after its first `stages` kernels (1 .. 4; 4 is the
+ * whole call).  With stages < 4 no picture is left and every status becomes KGDET_JPEG_DECODE_STOPPED. */
+int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n,
+                             void *workspace, size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status,
+                             void *stream, int32_t stages);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

@@ -50,6 +50,13 @@ COCO_ORDER_MAX_LABELS = 64    # KGDET_COCO_ORDER_MAX_LABELS
 COCO_JSON_MAX_K = 1024        # KGDET_COCO_JSON_MAX_K: landmarks of a record kgdet_coco_json_write assembles in LDS
 DRAW_MAX_IMAGES, DRAW_MAX_ROWS, DRAW_MAX_K, DRAW_MAX_LABELS = 32, 1024, 1024, 64    # KGDET_DRAW_MAX_*: kgdet_draw_detections
 JPEG_MAX_IMAGES, JPEG_RANGE_BYTES = 32, 4096    # KGDET_JPEG_*: kgdet_jpeg_encode (jpeg.py carries the same numbers)
+JPEG_DECODE_MAX_IMAGES, JPEG_DECODE_SUBSEQ_BITS, JPEG_DECODE_CHUNK_LANES, JPEG_DECODE_TABLE_BYTES = 32, 512, 1024, 1024   # KGDET_JPEG_DECODE_*
+
+
+class JpegDecodeJob(ctypes.Structure):
+    """kgdet_jpeg_decode_job (one file's scan and table block inside the source buffer -> one picture of the output buffer)"""
+    _fields_ = [(n, ctypes.c_int64) for n in ('scan_offset', 'scan_bytes', 'tables_offset', 'dst_offset')] + [
+        (n, ctypes.c_int32) for n in ('H', 'W', 'mode', 'reserved')]
 
 
 class CocoPackedDets(ctypes.Structure):
@@ -145,6 +152,14 @@ def lib():
             L.kgdet_jpeg_encode.restype = L.kgdet_jpeg_write.restype = ctypes.c_int
             L.kgdet_jpeg_encode.argtypes = [vp, i64, vp, i32, i32, vp, ctypes.c_size_t, vp, vp]
             L.kgdet_jpeg_write.argtypes = [vp, i32, i32, vp, ctypes.c_size_t, vp, vp, i64, vp, vp]
+        if hasattr(L, 'kgdet_jpeg_decode'):          # jpeg.py: a host job table, int64 and size_t sizes among the arguments
+            vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
+            L.kgdet_jpeg_decode_workspace_bytes.restype = ctypes.c_size_t
+            L.kgdet_jpeg_decode_workspace_bytes.argtypes = [vp, i32]
+            L.kgdet_jpeg_decode.restype = ctypes.c_int
+            L.kgdet_jpeg_decode.argtypes = [vp, i64, vp, i32, vp, ctypes.c_size_t, vp, i64, vp, vp]
+            L.kgdet_jpeg_decode_stages.restype = ctypes.c_int
+            L.kgdet_jpeg_decode_stages.argtypes = L.kgdet_jpeg_decode.argtypes + [i32]
         _lib = L
     return _lib
 

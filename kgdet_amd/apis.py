@@ -35,7 +35,7 @@ def train_detector(model, dataset, cfg, validate=False, logger=None):
     """``mmdet.apis.train_detector`` (the ``_non_dist_train`` flow) -> the ``Runner`` after ``cfg.total_epochs``.
 
     The loader is ``build_dataloader(dataset, cfg.data.imgs_per_gpu, cfg.data.workers_per_gpu, device=<the model's GPU>)``; the
-    optional config key ``loader = dict(device_preprocess=..., prefetch=...)`` picks the feed's route (absent: host pixels,
+    optional config key ``loader = dict(device_preprocess=..., device_decode=..., prefetch=...)`` picks the feed's route (absent: host pixels,
     uploaded from page-locked memory).  The runner takes ``cfg.lr_config``, ``cfg.optimizer_config``, ``cfg.checkpoint_config``,
     ``cfg.log_config.interval`` and ``cfg.work_dir``; ``cfg.resume_from`` / ``cfg.load_from`` are honoured in that order.
     ``validate=True``: ``cfg.data.val`` (built in test mode) is evaluated after every ``cfg.evaluation.interval``-th epoch
@@ -50,8 +50,10 @@ def train_detector(model, dataset, cfg, validate=False, logger=None):
     device = next(model.parameters()).device
     opts = dict(_get(cfg, 'loader', {}))
     device_preprocess = bool(opts.get('device_preprocess', False))
+    device_decode = bool(opts.get('device_decode', False))
     loader = build_dataloader(dataset, cfg.data.imgs_per_gpu, cfg.data.workers_per_gpu, _get(cfg, 'gpus', 1), dist=False,
-                              device=device, device_preprocess=device_preprocess, prefetch=opts.get('prefetch', 2))
+                              device=device, device_preprocess=device_preprocess, prefetch=opts.get('prefetch', 2),
+                              device_decode=device_decode)
     optimizer = build_optimizer(model, cfg.optimizer)
     work_dir = _get(cfg, 'work_dir')
     log_path = None
@@ -70,7 +72,7 @@ def train_detector(model, dataset, cfg, validate=False, logger=None):
     if validate:
         val = ds.build_dataset(cfg.data.val, dict(test_mode=True))
         eval_config = dict(dataset=val, interval=dict(_get(cfg, 'evaluation', {})).get('interval', 1),
-                           imgs_per_gpu=cfg.data.imgs_per_gpu, device_preprocess=device_preprocess,
+                           imgs_per_gpu=cfg.data.imgs_per_gpu, device_preprocess=device_preprocess, device_decode=device_decode,
                            workers=min(cfg.data.workers_per_gpu, 16), to_device=lambda t: t.to(device, non_blocking=True))
     runner = Runner(model, optimizer, work_dir=work_dir, lr_config=_get(cfg, 'lr_config'),
                     optimizer_config=_get(cfg, 'optimizer_config'), checkpoint_config=_get(cfg, 'checkpoint_config'),

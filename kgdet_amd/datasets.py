@@ -208,6 +208,26 @@ class DeepFashion2Dataset(object):
         with Image.open(os.path.join(self.img_prefix, self.img_infos[idx]['filename'])) as im:
             return np.array(im.convert('RGB'))
 
+    def load_image_file(self, idx):
+        """the image's FILE for the device decoder (``jpeg.DeviceDecodeRoute``): an ``EncodedImage`` with the file's bytes and
+        ``shape`` = (H, W, 3) from its header.  A file the decoder does not take (``jpeg.parse_header``'s ``reason``) is decoded
+        with PIL right here -- on the thread that read it, with one warning per file that names it and the reason -- and carried as
+        ``pixels``: the bits ``load_image`` returns."""
+        from . import jpeg
+        name = os.path.join(self.img_prefix, self.img_infos[idx]['filename'])
+        with open(name, 'rb') as f:
+            data = f.read()
+        frame = jpeg.parse_header(data)
+        if isinstance(frame, str):
+            warned = self.__dict__.setdefault('_decode_warned', set())
+            if name not in warned:                   # (once per file, not once per epoch)
+                import warnings
+                warned.add(name)
+                warnings.warn('%s: not a file the device JPEG decoder takes (%s); decoded on the host' % (name, frame))
+            pixels = jpeg.decode_pil(data)           # (the bytes already read: what load_image makes of the file)
+            return EncodedImage(data, pixels.shape, None, frame, name, pixels)
+        return EncodedImage(data, (frame['H'], frame['W'], 3), frame, None, name, None)
+
     def _sample_scale(self):
         scales, n = self.img_scales, len(self.img_scales)
         if n == 1:
@@ -288,7 +308,9 @@ class DeepFashion2Dataset(object):
         """``prepare_train_img`` without the pixel work: ``raw`` (the decoded uint8 H x W x 3 image), the drawn ``scale`` and
         ``flip`` (the same draws from numpy's global RNG, in the same order), ``keep_ratio``, the planned ``img_meta`` and
         the transformed ground truth -- a sample for ``collate_device``.  ``aug_plan``: the ``extra_aug`` draws (absent
-        without the keyword); the meta and the ground truth are then those of the plan's virtual image."""
+        without the keyword); the meta and the ground truth are then those of the plan's virtual image.  ``img`` may be an
+        ``EncodedImage`` (``load_image_file``): only its ``shape`` enters the draws and the plans, so they are those of the
+        decoded image, and it is carried as ``raw`` for ``jpeg.DeviceDecodeRoute`` to decode."""
         info = self.img_infos[idx]
         img = self.load_image(idx) if img is None else img
         ann = self.get_ann_info(idx)
@@ -298,7 +320,7 @@ class DeepFashion2Dataset(object):
         flip = bool(np.random.rand() < self.flip_ratio)
         scale = self._sample_scale()
         _, _, img_shape, pad_shape, sf = self._plan(img, scale, aug)
-        data = dict(raw=torch.from_numpy(np.ascontiguousarray(img)), scale=scale, flip=flip,
+        data = dict(raw=_as_raw(img), scale=scale, flip=flip,
                     keep_ratio=self.resize_keep_ratio, img_meta=self._meta(info, img_shape, pad_shape, sf, flip),
                     gt_bboxes=torch.from_numpy(bbox_transform(ann['bboxes'], img_shape, sf, flip)))
         if self.with_label:
@@ -320,7 +342,8 @@ class DeepFashion2Dataset(object):
 
     def prepare_test_raw(self, idx, img=None):
         """``prepare_test_img`` without the pixel work: ``raw`` (uint8 H x W x 3) once, and per augmentation -- in
-        ``prepare_test_img``'s order -- its ``scales`` / ``flips`` entry and planned ``img_meta``"""
+        ``prepare_test_img``'s order -- its ``scales`` / ``flips`` entry and planned ``img_meta``.  An ``EncodedImage`` given as
+        ``img`` is carried as ``raw`` (``prepare_train_raw``)"""
         info = self.img_infos[idx]
         img = self.load_image(idx) if img is None else img
         scales, flips, metas = [], [], []
@@ -330,8 +353,7 @@ class DeepFashion2Dataset(object):
                 scales.append(scale)
                 flips.append(flip)
                 metas.append(self._meta(info, img_shape, pad_shape, sf, flip))
-        return dict(raw=torch.from_numpy(np.ascontiguousarray(img)), scales=scales, flips=flips,
-                    keep_ratio=self.resize_keep_ratio, img_meta=metas)
+        return dict(raw=_as_raw(img), scales=scales, flips=flips, keep_ratio=self.resize_keep_ratio, img_meta=metas)
 
     def device_transform(self, device=None):
         """the ``DeviceImageTransform`` with this dataset's normalisation and ``size_divisor``"""
@@ -346,6 +368,20 @@ class DeepFashion2Dataset(object):
             if data is not None:
                 return data
             idx = int(np.random.choice(np.where(self.flag == self.flag[idx])[0]))
+
+
+class EncodedImage(object):
+    """an image as its file: ``data`` (bytes), ``shape`` = (H, W, 3) from the header, ``frame`` (``jpeg.parse_header``'s
+    description) -- or, for a file the device decoder does not take, ``reason`` and the PIL-decoded ``pixels``; ``name``: the
+    file, for messages"""
+    __slots__ = ('data', 'shape', 'frame', 'reason', 'name', 'pixels')
+
+    def __init__(self, data, shape, frame, reason, name, pixels):
+        self.data, self.shape, self.frame, self.reason, self.name, self.pixels = data, tuple(shape), frame, reason, name, pixels
+
+
+def _as_raw(img):
+    return img if isinstance(img, EncodedImage) else torch.from_numpy(np.ascontiguousarray(img))
 
 
 def finish_train_sample(dataset, raw_sample):

@@ -1,4 +1,6 @@
-"""Baseline JPEG files of the drawn pictures made on the GPU: ``jpeg_restatement``, ``DeviceJpegEncoder``, ``encode_jpeg``.
+"""Baseline JPEG on the GPU, both ways.  Files of the drawn pictures: ``jpeg_restatement``, ``DeviceJpegEncoder``, ``encode_jpeg``
+(this docstring).  Pictures of JPEG files, for the loader and the test loop: ``parse_header``, ``decode_restatement`` (the
+definition, in its docstring), ``DeviceJpegDecoder``, ``decode_jpeg``, ``DeviceDecodeRoute`` (the second half of the module).
 
 ``visualize.DeviceDrawer`` leaves a finished picture in device memory; ``kgdet_jpeg_encode`` / ``kgdet_jpeg_write``
 (csrc/jpeg.hip) turn that buffer into the bytes of the ``.jpg`` file, so that only compressed bytes come down.  The file is
@@ -375,3 +377,678 @@ def encode_jpeg(image, quality=90):
     if torch.is_tensor(image):
         image = image.cpu().numpy()
     return jpeg_restatement(image, quality)
+
+
+# ---- decoding ----------------------------------------------------------------------------------------------------------------
+DECODE_MAX_IMAGES = 32      # KGDET_JPEG_DECODE_MAX_IMAGES: images of one call
+DECODE_SUBSEQ_BITS = 512    # KGDET_JPEG_DECODE_SUBSEQ_BITS: bits of the un-stuffed stream one lane of the Huffman kernel owns
+DECODE_CHUNK_LANES = 1024   # KGDET_JPEG_DECODE_CHUNK_LANES: subsequences a workgroup brings to their fixpoint together
+DECODE_TABLE_BYTES = 1024   # KGDET_JPEG_DECODE_TABLE_BYTES: the table block of one image inside the source buffer
+MODE_GREY, MODE_444, MODE_420 = 0, 1, 2         # KGDET_JPEG_DECODE_GREY / _444 / _420
+BLOCKS_PER_MCU = (1, 3, 6)
+INVALID = (-1, -1, -1)      # the state of a parse that met an unmatched code or left the block: equal to no valid state
+
+IDCT_CONST = dict(c0_298=2446, c0_390=3196, c0_541=4433, c0_765=6270, c0_899=7373, c1_175=9633, c1_501=12299, c1_847=15137,
+                  c1_961=16069, c2_053=16819, c2_562=20995, c3_072=25172)
+
+
+def _kraft_ok(bits):
+    code = 0
+    for length in range(1, 17):
+        code += bits[length - 1]
+        if code > (1 << length):
+            return False
+        code <<= 1
+    return True
+
+
+def parse_header(data):
+    """Walk the segments of a JPEG file up to the end of ``SOS`` (segment lengths only; no entropy byte is touched) -> the frame
+    description the decoder needs, or a REASON STRING (in the style of ``head_loss.why_not``) for a file it does not take.
+
+    Taken: ``SOF0`` with 8-bit samples, 1 <= H, W <= 8192; one interleaved scan (Ss = 0, Se = 63, Ah = Al = 0) of three components
+    sampled 2x2 / 1x1 / 1x1 or 1x1 / 1x1 / 1x1 -- YCbCr: a JFIF ``APP0`` or the ids 1, 2, 3 -- or of one component; 8-bit
+    quantisation tables; DC and AC Huffman tables 0 and 1; several tables in one ``DQT`` / ``DHT``; any ``APPn`` / ``COM``
+    and fill 0xFF bytes; ``DRI`` 0.  Everything else -- progressive, extended, lossless and arithmetic frames, other samplings, a
+    restart interval, ``APP14`` Adobe, 16-bit tables, four components, H = 0 (``DNL``), more than one scan -- gives its reason.
+
+    The description: dict(H, W, ncomp, mode, qt uint8 [3, 64] natural order per component, dc / ac {id: (bits, vals)},
+    comp_dc / comp_ac [3], scan_offset, tables = the ``DECODE_TABLE_BYTES`` block ``kgdet_jpeg_decode`` reads)."""
+    data = bytes(data)
+    if data[:2] != b'\xff\xd8':
+        return 'no SOI marker'
+    at, size = 2, len(data)
+    qt, dc, ac = {}, {}, {}
+    sof, jfif = None, False
+    while True:
+        if at + 4 > size:
+            return 'the file ends inside its header'
+        if data[at] != 0xFF:
+            return 'no marker at byte %d' % at
+        while data[at + 1] == 0xFF:                     # fill bytes
+            at += 1
+            if at + 4 > size:
+                return 'the file ends inside its header'
+        marker = data[at + 1]
+        if marker == 0xD9:
+            return 'EOI before any scan'
+        if marker == 0x01 or 0xD0 <= marker <= 0xD7:
+            return 'marker %02X in the header' % marker
+        n = data[at + 2] << 8 | data[at + 3]
+        if n < 2 or at + 2 + n > size:
+            return 'segment %02X runs past the file' % marker
+        body = data[at + 4:at + 2 + n]
+        if marker == 0xE0:
+            jfif = jfif or body[:5] == b'JFIF\x00'
+        elif marker == 0xEE and body[:5] == b'Adobe':
+            return 'APP14 Adobe segment (its colour transform is not read)'
+        elif 0xE0 <= marker <= 0xEF or marker == 0xFE:
+            pass
+        elif marker == 0xDB:
+            k = 0
+            while k < len(body):
+                pq, tq = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    return '16-bit quantisation table'
+                if tq > 3 or k + 65 > len(body):
+                    return 'malformed DQT segment'
+                table = np.zeros(64, dtype=np.uint8)
+                table[ZIGZAG] = list(body[k + 1:k + 65])
+                qt[tq] = table
+                k += 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(body):
+                tc, th = body[k] >> 4, body[k] & 15
+                if k + 17 > len(body):
+                    return 'malformed DHT segment'
+                bits = list(body[k + 1:k + 17])
+                count = sum(bits)
+                if tc > 1 or k + 17 + count > len(body) or count > (256 if tc else 16) or not _kraft_ok(bits):
+                    return 'malformed DHT segment'
+                if th > 1:
+                    return 'Huffman table %d (tables 0 and 1 are read)' % th
+                (ac if tc else dc)[th] = (bits, list(body[k + 17:k + 17 + count]))
+                k += 17 + count
+        elif marker == 0xC0:
+            if sof is not None:
+                return 'two frame headers'
+            if n < 8 or n != 8 + 3 * body[5]:
+                return 'malformed SOF0 segment'
+            comps = [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(body[5])]
+            sof = (body[0], body[1] << 8 | body[2], body[3] << 8 | body[4], comps)
+        elif marker in (0xC1, 0xC2, 0xC3, 0xC5, 0xC6, 0xC7, 0xC8, 0xC9, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF):
+            kind = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless'}.get(marker, 'arithmetic-coded' if marker >= 0xC9
+                                                                                             else 'differential')
+            return '%s frame (SOF%d)' % (kind, marker - 0xC0) if marker != 0xCC else 'arithmetic coding (DAC)'
+        elif marker == 0xDD:
+            if n != 4:
+                return 'malformed DRI segment'
+            if body[0] << 8 | body[1]:
+                return 'restart interval %d (DRI)' % (body[0] << 8 | body[1])
+        elif marker == 0xDC:
+            return 'DNL segment'
+        elif marker == 0xDA:
+            break
+        else:
+            return 'unexpected marker %02X' % marker
+        at += 2 + n
+    if sof is None:
+        return 'SOS before the frame header'
+    precision, H, W, comps = sof
+    if precision != 8:
+        return '%d-bit samples' % precision
+    if H == 0:
+        return 'H = 0 (the height comes in a DNL segment)'
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        return 'image of %d x %d (sides 1 .. %d)' % (H, W, MAX_SIDE)
+    if len(comps) == 4:
+        return 'four components'
+    if len(comps) not in (1, 3):
+        return '%d components' % len(comps)
+    sampling = [c[1:3] for c in comps]
+    if len(comps) == 1:
+        mode = MODE_GREY
+    elif sampling == [(2, 2), (1, 1), (1, 1)]:
+        mode = MODE_420
+    elif sampling == [(1, 1), (1, 1), (1, 1)]:
+        mode = MODE_444
+    else:
+        return 'sampling %s (2x2 / 1x1 / 1x1 and 1x1 / 1x1 / 1x1 are read)' % ' / '.join('%dx%d' % s for s in sampling)
+    if len(comps) == 3 and not (jfif or [c[0] for c in comps] == [1, 2, 3]):
+        return 'three components that are not marked as YCbCr (no JFIF APP0, ids %s)' % ', '.join(str(c[0]) for c in comps)
+    if n < 6 or body[0] < 1 or n != 6 + 2 * body[0]:
+        return 'malformed SOS segment'
+    if body[0] != len(comps):
+        return 'more than one scan (a scan of %d of %d components)' % (body[0], len(comps))
+    comp_dc, comp_ac = [0, 0, 0], [0, 0, 0]
+    for i, c in enumerate(comps):
+        cid, td, ta = body[1 + 2 * i], body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15
+        if cid != c[0]:
+            return 'the scan names component %d where the frame has %d' % (cid, c[0])
+        if td not in dc or ta not in ac:
+            return 'the scan names a Huffman table the file does not define'
+        if c[3] not in qt:
+            return 'the frame names a quantisation table the file does not define'
+        comp_dc[i], comp_ac[i] = td, ta
+    if tuple(body[1 + 2 * body[0]:]) != (0, 63, 0):
+        return 'spectral selection or successive approximation in a baseline scan'
+    Q = np.stack([qt[comps[min(i, len(comps) - 1)][3]] for i in range(3)])
+    blob = bytearray(DECODE_TABLE_BYTES)
+    blob[0:192] = Q.tobytes()
+    for t in range(2):
+        for tables, bits_at, vals_at, room in ((dc, 192, 224, 16), (ac, 256, 288, 256)):
+            if t in tables:
+                bits, vals = tables[t]
+                blob[bits_at + 16 * t:bits_at + 16 * t + 16] = bytes(bits)
+                blob[vals_at + room * t:vals_at + room * t + len(vals)] = bytes(vals)
+    blob[800:803], blob[803:806] = bytes(comp_dc), bytes(comp_ac)
+    return dict(H=H, W=W, ncomp=len(comps), mode=mode, qt=Q, dc=dc, ac=ac, comp_dc=comp_dc, comp_ac=comp_ac,
+                scan_offset=at + 2 + n, tables=bytes(blob))
+
+
+def frame_blocks(frame):
+    """(MCUs per row, MCU rows, blocks per MCU) of a frame; a one-component scan is not padded to an MCU: its MCU is a block"""
+    unit = 16 if frame['mode'] == MODE_420 else 8
+    return (frame['W'] + unit - 1) // unit, (frame['H'] + unit - 1) // unit, BLOCKS_PER_MCU[frame['mode']]
+
+
+def unstuff(data, scan_offset):
+    """the scan's bytes with the 0xFF 0x00 stuffing removed: it ends at the first 0xFF that a byte other than 0x00 follows, which
+    has to be ``EOI``; bytes behind it are ignored"""
+    k = data.find(b'\xff', scan_offset)
+    while k >= 0 and k + 1 < len(data) and data[k + 1] == 0:
+        k = data.find(b'\xff', k + 2)
+    if k < 0 or k + 1 >= len(data):
+        raise ValueError('no marker ends the scan')
+    if data[k + 1] != 0xD9:
+        raise ValueError('marker %02X ends the scan, not EOI' % data[k + 1])
+    return data[scan_offset:k].replace(b'\xff\x00', b'\xff')
+
+
+def _lookup(bits, vals):
+    """(symbol, length) by the next 16 bits: two lists of 65536, length 0 where no code matches"""
+    sym, length_of = np.zeros(65536, dtype=np.int64), np.zeros(65536, dtype=np.int64)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            lo = code << (16 - length)
+            sym[lo:lo + (1 << (16 - length))] = vals[k]
+            length_of[lo:lo + (1 << (16 - length))] = length
+            code, k = code + 1, k + 1
+        code <<= 1
+    return sym.tolist(), length_of.tolist()
+
+
+class EntropyContext(object):
+    """the un-stuffed stream of a file with what ``decode_span`` needs: ``window[p]`` = the 32 bits from bit p (1-bits behind the
+    end), the look-ups of each block slot of the MCU, ``total_bits``"""
+
+    def __init__(self, frame, stream):
+        self.frame, self.stream, self.total_bits = frame, stream, 8 * len(stream)
+        bit = np.unpackbits(np.frombuffer(stream + b'\xff' * 5, dtype=np.uint8)).astype(np.int64)
+        window = np.zeros(self.total_bits + 1, dtype=np.int64)
+        for j in range(32):
+            window += bit[j:j + self.total_bits + 1] << (31 - j)
+        self.window = window.tolist()
+        self.bpm = BLOCKS_PER_MCU[frame['mode']]
+        comp = {MODE_GREY: (0,), MODE_444: (0, 1, 2), MODE_420: (0, 0, 0, 0, 1, 2)}[frame['mode']]
+        luts = {}
+        for kind, tables in (('dc', frame['dc']), ('ac', frame['ac'])):
+            for t, (bits, vals) in tables.items():
+                luts[kind, t] = _lookup(bits, vals)
+        self.slot_comp = comp
+        self.slot_tables = [(luts['dc', frame['comp_dc'][c]], luts['ac', frame['comp_ac'][c]]) for c in comp]
+
+
+def decode_span(ctx, state, limit, sink=None, trace=None):
+    """Decode the symbols that START before bit ``limit`` from ``state`` = (bit position, block slot inside the MCU, zigzag
+    index; index 0: the next symbol is a DC code) -> (the exit state, blocks completed).  This is the step the Huffman kernel
+    takes per lane, for a true state and for a speculative one alike:
+    - a symbol (code and magnitude bits) that would run past the stream's last bit is not taken, and neither is an unmatched
+      code within the last 15 bits (read with 1-bits behind the end, no code fits what is left): the span stops in front of it;
+    - an unmatched code, a DC category above 11, an AC category above 10, a (run, 0) symbol other than EOB and ZRL, and a zigzag
+      index past 63 (a ZRL that reaches the block's end included) give ``INVALID``; ``INVALID`` stays ``INVALID``.
+    ``sink(block, zigzag index, value)`` receives the coefficients (a DC value is the difference), ``block`` counted from the
+    span's start; ``trace`` (a list) receives (position, code bits, magnitude bits, symbol, zigzag index, block completed)."""
+    if state == INVALID:
+        return INVALID, 0
+    p, b, z = state
+    done, total, window, bpm = 0, ctx.total_bits, ctx.window, ctx.bpm
+    while p < limit and p < total:
+        w = window[p]
+        (dsym, dlen), (asym, alen) = ctx.slot_tables[b]
+        ends = False
+        if z == 0:
+            length = dlen[w >> 16]
+            if length == 0:
+                if total - p < 16:
+                    break
+                return INVALID, done
+            s = run = dsym[w >> 16]
+            if s > 11:
+                return INVALID, done
+            place = 0
+        else:
+            length = alen[w >> 16]
+            if length == 0:
+                if total - p < 16:
+                    break
+                return INVALID, done
+            rs = asym[w >> 16]
+            run, s = rs >> 4, rs & 15
+            if s == 0:
+                if run == 15:
+                    if z + 16 > 63:
+                        return INVALID, done
+                elif run != 0:
+                    return INVALID, done
+            else:
+                if z + run > 63 or s > 10:
+                    return INVALID, done
+            place = z + run
+        if p + length + s > total:
+            break
+        if z == 0 or s:
+            if s:
+                v = (w >> (32 - length - s)) & ((1 << s) - 1)
+                if not v >> (s - 1):
+                    v -= (1 << s) - 1
+            else:
+                v = 0
+            if sink is not None and (s or z == 0):
+                sink(done, place, v)
+            nz = place + 1
+            ends = nz == 64
+        elif run == 15:
+            nz = z + 16
+        else:
+            nz, ends = 0, True
+        if trace is not None:
+            trace.append((p, length, s, -1 if z == 0 else (run << 4 | s), z, ends))
+        p += length + s
+        if ends:
+            z = 0
+            b = b + 1 if b + 1 < bpm else 0
+            done += 1
+        else:
+            z = nz
+    return (p, b, z), done
+
+
+def _idct_1d(x, shift):
+    """libjpeg's jidctint.c (islow) butterfly along the last axis of int64 [..., 8], then (v + 2^(shift - 1)) >> shift"""
+    F = IDCT_CONST
+    i0, i1, i2, i3, i4, i5, i6, i7 = [x[..., n] for n in range(8)]
+    z1 = (i2 + i6) * F['c0_541']
+    t2, t3 = z1 - i6 * F['c1_847'], z1 + i2 * F['c0_765']
+    t0, t1 = (i0 + i4) << 13, (i0 - i4) << 13
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    o0, o1, o2, o3 = i7, i5, i3, i1
+    z1, z2, z3, z4 = o0 + o3, o1 + o2, o0 + o2, o1 + o3
+    z5 = (z3 + z4) * F['c1_175']
+    o0, o1, o2, o3 = o0 * F['c0_298'], o1 * F['c2_053'], o2 * F['c3_072'], o3 * F['c1_501']
+    z1, z2 = -z1 * F['c0_899'], -z2 * F['c2_562']
+    z3, z4 = -z3 * F['c1_961'] + z5, -z4 * F['c0_390'] + z5
+    o0, o1, o2, o3 = o0 + z1 + z3, o1 + z2 + z4, o2 + z2 + z3, o3 + z1 + z4
+    out = [t10 + o3, t11 + o2, t12 + o1, t13 + o0, t13 - o0, t12 - o1, t11 - o2, t10 - o3]
+    return np.stack([(v + (1 << (shift - 1))) >> shift for v in out], axis=-1)
+
+
+def idct_blocks(levels, q):
+    """int64 [a, b, 8, 8] levels and a table [64] (natural order) -> the samples int64 [8 a, 8 b] in 0 .. 255"""
+    a, b = levels.shape[:2]
+    f = levels.astype(np.int64) * q.reshape(8, 8).astype(np.int64)
+    ws = _idct_1d(f.transpose(0, 1, 3, 2), 11).transpose(0, 1, 3, 2)        # pass 1: down the columns
+    out = _idct_1d(ws, 18) + 128                                            # pass 2: along the rows
+    return np.clip(out, 0, 255).transpose(0, 2, 1, 3).reshape(8 * a, 8 * b)
+
+
+def fancy_upsample(c, ch, cw):
+    """libjpeg's triangle ("fancy") h2v2 upsampling of the real extent [ch, cw] of a chroma plane -> int64 [2 ch, 2 cw]"""
+    c = c[:ch, :cw].astype(np.int64)
+    up, dn = np.concatenate([c[:1], c[:-1]]), np.concatenate([c[1:], c[-1:]])
+    rows = np.empty((2 * ch, cw), dtype=np.int64)
+    rows[0::2], rows[1::2] = 3 * c + up, 3 * c + dn
+    left, right = np.concatenate([rows[:, :1], rows[:, :-1]], 1), np.concatenate([rows[:, 1:], rows[:, -1:]], 1)
+    out = np.empty((2 * ch, 2 * cw), dtype=np.int64)
+    out[:, 0::2], out[:, 1::2] = (3 * rows + left + 8) >> 4, (3 * rows + right + 7) >> 4
+    return out
+
+
+def decode_parts(data, trace=None):
+    """the restatement with its intermediate results: dict(frame, stream, coefficients int64 [blocks, 64] natural order in
+    scan order with the DC values summed, planes, image)"""
+    data = bytes(data)
+    frame = parse_header(data)
+    if isinstance(frame, str):
+        raise ValueError('decode_restatement does not read this file: %s' % frame)
+    stream = unstuff(data, frame['scan_offset'])
+    ctx = EntropyContext(frame, stream)
+    mw, mh, bpm = frame_blocks(frame)
+    nblocks = mw * mh * bpm
+    zz = np.zeros((nblocks + 1, 64), dtype=np.int64)
+
+    def sink(block, place, value):
+        zz[min(block, nblocks), place] = value
+    state, done = decode_span(ctx, (0, 0, 0), ctx.total_bits, sink, trace)
+    if state == INVALID:
+        raise ValueError('the scan holds an invalid code')
+    if done != nblocks or state[2] != 0 or not 0 <= ctx.total_bits - state[0] < 8:
+        raise ValueError('the scan holds %d blocks and ends %d bits before its data does; the frame has %d blocks'
+                         % (done, ctx.total_bits - state[0], nblocks))
+    zz = zz[:nblocks].reshape(mw * mh, bpm, 64)
+    for slots in {MODE_GREY: ((0,),), MODE_444: ((0,), (1,), (2,)), MODE_420: ((0, 1, 2, 3), (4,), (5,))}[frame['mode']]:
+        dc = zz[:, slots, 0]
+        zz[:, slots, 0] = np.cumsum(dc.reshape(-1)).reshape(dc.shape)
+    zz = np.clip(zz, -32768, 32767)
+    coef = np.zeros_like(zz)
+    coef[..., ZIGZAG] = zz
+    grid = coef.reshape(mh, mw, bpm, 8, 8)
+    H, W, Q = frame['H'], frame['W'], frame['qt']
+    if frame['mode'] == MODE_420:
+        luma = grid[:, :, :4].reshape(mh, mw, 2, 2, 8, 8).transpose(0, 2, 1, 3, 4, 5).reshape(2 * mh, 2 * mw, 8, 8)
+        ch, cw = (H + 1) // 2, (W + 1) // 2
+        planes = [idct_blocks(luma, Q[0])[:H, :W]] + [fancy_upsample(idct_blocks(grid[:, :, 3 + c], Q[c]), ch, cw)[:H, :W]
+                                                     for c in (1, 2)]
+    else:
+        planes = [idct_blocks(grid[:, :, c], Q[c])[:H, :W] for c in range(bpm)]
+    if frame['mode'] == MODE_GREY:
+        rgb = np.stack([planes[0]] * 3, -1)
+    else:
+        Y, cb, cr = planes[0], planes[1] - 128, planes[2] - 128
+        rgb = np.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16),
+                        Y + ((116130 * cb + 32768) >> 16)], -1)
+    image = np.clip(rgb, 0, 255).astype(np.uint8)
+    return dict(frame=frame, stream=stream, context=ctx, coefficients=coef.reshape(nblocks, 64), planes=planes, image=image)
+
+
+def decode_restatement(data):
+    """The picture of a JPEG file ``parse_header`` takes -> uint8 [H, W, 3] RGB: the definition ``kgdet_jpeg_decode`` is held to
+    bit for bit, itself held to PIL's decoder (libjpeg-turbo), which is what ``DeepFashion2Dataset.load_image`` returns.
+
+    1. Entropy layer: ``unstuff``, then ``decode_span`` from (0, 0, 0) over the whole stream.  The scan has to hold exactly the
+       frame's blocks and end within the last byte of its data; the DC values are the running sums of the differences per
+       component.  Levels are clamped to -32768 .. 32767 (a file made from pixels stays within +-2048).
+    2. Dequantisation, level * q in natural order.
+    3. libjpeg's ``islow`` inverse DCT (CONST_BITS 13, PASS1_BITS 2, the constants ``IDCT_CONST``): pass 1 down the columns with
+       (x + 2^10) >> 11, pass 2 along the rows with (x + 2^17) >> 18, + 128, clamped to 0 .. 255.
+    4. Chroma of 2x2-sampled files: libjpeg's "fancy" triangle upsampling over the real extent ceil(H / 2) x ceil(W / 2):
+       v = 3 c[r] + c[r -/+ 1] for the upper / lower output row, then (3 v[x] + v[x - 1] + 8) >> 4 for an even and
+       (3 v[x] + v[x + 1] + 7) >> 4 for an odd output column, the neighbour replicated at every edge.
+    5. Colour, cb and cr the samples minus 128, arithmetic shifts, clamped: R = Y + ((91881 cr + 32768) >> 16),
+       G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16); one component gives R = G = B = Y.
+
+    Pinned domain: equality with PIL holds for files an encoder made from pixels (tests/test_jpeg_decode_refs.py).  A patched
+    file whose dequantised coefficients overflow 16-bit intermediates is outside it: libjpeg-turbo's SIMD inverse DCT wraps
+    there, where this definition (64-bit integers) and the kernels clamp and agree with each other.  Raises ``ValueError``
+    for a file ``parse_header`` refuses and for a scan that is malformed; PIL is more lenient with both."""
+    return decode_parts(data)['image']
+
+
+def _align(v, a):
+    return (v + a - 1) // a * a
+
+
+def pack_files(files, frames, into=None):
+    """Lay the scans (from the first entropy byte to the file's end) and the table blocks of ``files`` out in one buffer, each
+    at a multiple of 16 bytes -> (bytes used, [(scan offset, scan bytes, tables offset)]); ``into``: a uint8 numpy array that
+    receives them (None: only the layout)"""
+    at, places = 0, []
+    for data, frame in zip(files, frames):
+        scan = len(data) - frame['scan_offset']
+        places.append((at, scan, at + _align(scan, 16)))
+        if into is not None:
+            into[at:at + scan] = np.frombuffer(data, dtype=np.uint8, offset=frame['scan_offset'])
+            into[places[-1][2]:places[-1][2] + DECODE_TABLE_BYTES] = np.frombuffer(frame['tables'], dtype=np.uint8)
+        at = places[-1][2] + DECODE_TABLE_BYTES
+    return at, places
+
+
+class DeviceJpegDecoder(object):
+    """``kgdet_jpeg_decode``.  ``decoder(files)``: ``files`` a list of ``bytes`` that ``parse_header`` takes (``frames``: their
+    descriptions, when the caller has parsed them already) -> ``(images, status)``: ``images`` uint8 [H, W, 3] device tensors,
+    views of ONE buffer, bit for bit ``decode_restatement``'s; ``status`` the device int32 [n] tensor of the kernels' verdicts
+    (0: decoded; else the image's pixels mean nothing).  Nothing is read back here: the caller looks at ``status`` when it
+    needs the pictures.  The files travel through one page-locked staging copy and one non-blocking upload, as
+    ``DeviceImageTransform._upload``'s images do; everything runs on the device's current stream.  The workspace grows to the
+    largest group seen (about 3.5 bytes per pixel of a 4:2:0 picture) and is reused: every call makes its stream wait for the
+    event behind the previous call, so the object may be used from any stream (one thread at a time)."""
+
+    def __init__(self, device=None):
+        import torch
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.workspace = None
+        self._pinned = None
+        self._pinned_free = None
+        self._last = None                    # event behind the last call's kernels: the next call's stream waits for it
+        self.uploaded = 0                    # bytes of files uploaded so far (tools/time_jpeg_decode.py)
+
+    def __call__(self, files, frames=None):
+        import torch
+        files = [bytes(f) for f in files]
+        frames = [parse_header(f) for f in files] if frames is None else list(frames)
+        for k, frame in enumerate(frames):
+            if isinstance(frame, str):
+                raise ValueError('file %d is not one the device decodes: %s' % (k, frame))
+        if not files:
+            return [], torch.empty(0, dtype=torch.int32, device=self.device)
+        total, places = pack_files(files, frames)
+        if self._pinned is None or self._pinned.numel() < total:
+            self._pinned = torch.empty(max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
+            self._pinned_free = None
+        if self._pinned_free is not None:
+            self._pinned_free.synchronize()          # (the previous call's upload still reads the buffer)
+        pack_files(files, frames, self._pinned.numpy())
+        with torch.cuda.device(self.device):
+            src = self._pinned[:total].to(self.device, non_blocking=True)
+            self._pinned_free = torch.cuda.Event()
+            self._pinned_free.record()
+        self.uploaded += total
+        jobs = [(so, sb, to, f['H'], f['W'], f['mode']) for (so, sb, to), f in zip(places, frames)]
+        return self.decode(src, jobs)
+
+    def decode(self, src, jobs, out=None, stages=4):
+        """the files' bytes already on the device: ``src`` a flat uint8 device tensor, ``jobs`` [(scan offset, scan bytes,
+        tables offset, H, W, mode)] with the offsets inside ``src`` -> ``(images, status)``; ``out``: a flat uint8 device tensor
+        to decode into (the pictures follow each other at multiples of 256 bytes).  ``stages`` < 4 (the timing tool's): only
+        the first kernels run, no picture is made and every status is -1.  The workspace is shared by the object's calls: a
+        call waits, on the device, for the previous one, whichever stream that ran on."""
+        import ctypes
+        import torch
+        from . import _lib
+        lib, p = _lib.lib(), _lib.ptr
+        dev = src.device
+        places, total = [], 0
+        for _, _, _, H, W, _ in jobs:
+            places.append(total)
+            total += _align(3 * H * W, 256)
+        if out is None:
+            out = torch.empty(total, dtype=torch.uint8, device=dev)
+        elif not (out.is_cuda and out.device == dev and out.dtype == torch.uint8 and out.dim() == 1 and out.numel() >= total):
+            raise ValueError('out must be a flat uint8 tensor of at least %d bytes on %s' % (total, dev))
+        status = torch.empty(len(jobs), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            stream = _lib.current_stream()
+            if self._last is not None:
+                torch.cuda.current_stream().wait_event(self._last)      # (no wait at all on the stream that recorded it)
+            for g in range(0, len(jobs), DECODE_MAX_IMAGES):
+                group = jobs[g:g + DECODE_MAX_IMAGES]
+                table = (_lib.JpegDecodeJob * len(group))(*[
+                    _lib.JpegDecodeJob(int(so), int(sb), int(to), places[g + k], int(H), int(W), int(mode), 0)
+                    for k, (so, sb, to, H, W, mode) in enumerate(group)])
+                n = ctypes.c_int32(len(group))
+                need = lib.kgdet_jpeg_decode_workspace_bytes(table, n)
+                if need == 0:
+                    _lib.check(_lib.KGDET_E_SHAPE, 'kgdet_jpeg_decode_workspace_bytes')
+                if self.workspace is None or self.workspace.numel() < need or self.workspace.device != dev:
+                    self.workspace = None
+                    self.workspace = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+                ws = self.workspace
+                _lib.check(lib.kgdet_jpeg_decode_stages(p(src), ctypes.c_int64(src.numel()), table, n, p(ws),
+                                                        ctypes.c_size_t(ws.numel()), p(out), ctypes.c_int64(out.numel()),
+                                                        p(status[g:g + len(group)]), stream, ctypes.c_int32(stages)),
+                           'kgdet_jpeg_decode')
+            self._last = torch.cuda.Event()
+            self._last.record()
+        images = [out[at:at + 3 * H * W].view(H, W, 3) for at, (_, _, _, H, W, _) in zip(places, jobs)]
+        return images, status
+
+    def rounds(self, n):
+        """rounds the fixpoint of the last call's first ``n`` images took, the largest over each image's chunks (a read-back)"""
+        import torch
+        return self.workspace[4 * DECODE_MAX_IMAGES:4 * DECODE_MAX_IMAGES + 4 * n].view(torch.int32).tolist()
+
+
+def decode_pil(data):
+    """the picture of a JPEG file by PIL, as ``DeepFashion2Dataset.load_image`` reads it -> uint8 [H, W, 3] RGB"""
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return np.array(im.convert('RGB'))
+
+
+_decoders = {}
+
+
+def decode_jpeg(data):
+    """the picture of a JPEG file -> uint8 [H, W, 3] RGB numpy array: by ``DeviceJpegDecoder`` when a GPU and the library are
+    there, ``parse_header`` takes the file and the kernels' status is 0; else by PIL.  On the pinned domain (see
+    ``decode_restatement``) both give the same bits."""
+    import torch
+    data = bytes(data)
+    if device_available():
+        frame = parse_header(data)
+        if not isinstance(frame, str):
+            dev = torch.cuda.current_device()
+            if dev not in _decoders:
+                _decoders[dev] = DeviceJpegDecoder(torch.device('cuda', dev))
+            images, status = _decoders[dev]([data], [frame])
+            if int(status[0]) == 0:
+                return images[0].cpu().numpy()
+    return decode_pil(data)
+
+
+class DeviceDecodeRoute(object):
+    """What the loader and the test loop do with ``datasets.EncodedImage`` samples: ``route(raws)`` -> the list with every
+    ``EncodedImage`` replaced by its picture -- a uint8 [H, W, 3] device tensor from ONE ``kgdet_jpeg_decode`` call per 32 files
+    (views of one buffer), or the PIL-decoded host tensor for a file the decoder does not take -- and everything else as it was.
+    The list is never handed out before the kernels' status is known: an image with non-zero status is decoded by PIL on the
+    spot (which raises for a truncated file exactly as ``load_image`` does) and one warning names the file.
+
+    Upload, decode and the status read-back run on a stream of the route's own, so that the read-back waits for the decode
+    alone and never for the work the consumer has queued (a training step); the consumer's current stream is then made to wait
+    for the decode's event, and the pictures are marked as used on it (``record_stream``).  ``start_block`` / ``finish_block``: the same in two halves for files
+    that already lie in a page-locked block (the loader's ring slot, ``pack_files``' layout at ``files_at``), which goes up in
+    one copy together with whatever else the block holds; it returns the device block too.  Between the halves nothing is waited for, so the loader
+    starts the next batch's decode while the consumer trains on this one."""
+
+    def __init__(self, device=None):
+        import torch
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.decoder = DeviceJpegDecoder(self.device)
+        self.stream = None
+        self._status = None
+        self._turn = 0
+        self.fallbacks = 0                   # images the kernels refused (decoded by PIL) so far
+
+    def _side(self):
+        import torch
+        if self.stream is None:
+            with torch.cuda.device(self.device):
+                self.stream = torch.cuda.Stream()
+                self._status = torch.empty((2, DECODE_MAX_IMAGES), dtype=torch.int32).pin_memory()
+        return self.stream
+
+    def __call__(self, raws):
+        import torch
+        raws = list(raws)
+        which = [k for k, r in enumerate(raws) if _is_encoded(r) and r.frame is not None]
+        out = [torch.from_numpy(np.ascontiguousarray(r.pixels)) if _is_encoded(r) and r.frame is None else r for r in raws]
+        for g in range(0, len(which), DECODE_MAX_IMAGES):
+            part = which[g:g + DECODE_MAX_IMAGES]
+            with torch.cuda.device(self.device):
+                consumer = torch.cuda.current_stream()
+                with torch.cuda.stream(self._side()):
+                    images, status = self.decoder([raws[k].data for k in part], [raws[k].frame for k in part])
+                    done = self._read_back(status)
+                for k, img in zip(part, self._finish(images, done, [raws[j] for j in part], consumer)):
+                    out[k] = img
+        return out
+
+    def start_block(self, pinned, files_at, places, raws):
+        """``pinned``: the page-locked block; ``places``: ``pack_files``' (scan offset, scan bytes, tables offset) relative to
+        ``files_at`` for the ``EncodedImage``s of ``raws`` that have a frame, in order (at most 32).  Issues the block's upload,
+        the decode and the status read-back on the route's stream and WAITS FOR NOTHING -> a handle for ``finish_block``, with
+        ``uploaded`` (the event behind the block's upload: the block may be written again once it has completed)."""
+        import torch
+        raws = list(raws)
+        which = [k for k, r in enumerate(raws) if _is_encoded(r) and r.frame is not None]
+        assert len(which) == len(places) <= DECODE_MAX_IMAGES
+        out = [torch.from_numpy(np.ascontiguousarray(r.pixels)) if _is_encoded(r) and r.frame is None else r for r in raws]
+        with torch.cuda.device(self.device):
+            with torch.cuda.stream(self._side()):
+                dev = pinned.to(self.device, non_blocking=True)
+                uploaded = torch.cuda.Event()
+                uploaded.record()
+                images, done, slot = [], None, self._turn
+                if which:
+                    jobs = [(files_at + so, sb, files_at + to, raws[k].frame['H'], raws[k].frame['W'], raws[k].frame['mode'])
+                            for k, (so, sb, to) in zip(which, places)]
+                    images, status = self.decoder.decode(dev, jobs)
+                    self._turn = 1 - slot                # (two handles may be open: each has its own page-locked status)
+                    done = self._read_back(status, slot)
+        return _Pending(dev, out, which, images, done, [raws[k] for k in which], uploaded, slot)
+
+    def finish_block(self, pending):
+        """-> (device block, pictures) of a ``start_block`` handle, on the consumer's current stream: waits for the decode's
+        event alone, then PIL for every image the kernels refused"""
+        import torch
+        with torch.cuda.device(self.device):
+            consumer = torch.cuda.current_stream()
+            if pending.done is None:
+                consumer.wait_event(pending.uploaded)
+            else:
+                pictures = self._finish(pending.images, pending.done, pending.encoded, consumer, pending.slot)
+                for k, img in zip(pending.which, pictures):
+                    pending.out[k] = img
+            pending.dev.record_stream(consumer)
+        return pending.dev, pending.out
+
+    def _read_back(self, status, slot=0):
+        """(on the side stream) the status into page-locked memory and the event behind it"""
+        import torch
+        self._status[slot, :status.numel()].copy_(status, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        return done
+
+    def _finish(self, images, done, encoded, consumer, slot=0):
+        import warnings
+        import torch
+        done.synchronize()                   # the decode's own stream: nothing of the consumer's queue is waited for
+        consumer.wait_event(done)
+        if images:
+            images[0].record_stream(consumer)            # (views of one buffer: one storage)
+        out = []
+        for img, enc, status in zip(images, encoded, self._status[slot, :len(images)].tolist()):
+            if status != 0:
+                self.fallbacks += 1
+                warnings.warn('%s: the device JPEG decoder refused the scan (status %d); decoded on the host'
+                              % (enc.name or 'an image', status))
+                img = torch.from_numpy(decode_pil(enc.data))
+            out.append(img)
+        return out
+
+
+class _Pending(object):
+    """a batch whose upload and decode ``DeviceDecodeRoute.start_block`` has issued"""
+
+    def __init__(self, dev, out, which, images, done, encoded, uploaded, slot):
+        self.dev, self.out, self.which, self.images, self.done = dev, out, which, images, done
+        self.encoded, self.uploaded, self.slot = encoded, uploaded, slot
+
+
+def _is_encoded(r):
+    from .datasets import EncodedImage
+    return isinstance(r, EncodedImage)

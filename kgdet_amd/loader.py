@@ -36,6 +36,19 @@ consumer allocates the slots, issues every upload and launch from inside ``__nex
 written again only after the event recorded behind its upload has completed.  That keeps the feed legal next to a stream
 capture on the consuming thread and the process at one GPU context.  No side stream is used: on one in-order stream the
 upload of a batch is issued when the batch is handed out (issuing it one batch earlier would change nothing there).
+
+``device_decode=True`` (with ``device_preprocess=True``): the pool only reads the files and parses their headers
+(``dataset.load_image_file``), the draws and plans use the header's shape, ``_stage`` packs the files' bytes into the ring slot
+behind the ground truth, and the consumer decodes the batch in one ``kgdet_jpeg_decode`` call (``jpeg.DeviceDecodeRoute``)
+before ``collate_device``.  The batches are bit for bit those of ``device_decode=False``.  A batch is handed out only once the
+decoder's status is known: an image it refused is decoded by PIL on the spot, with a warning.  This route DOES use a side
+stream, for the block's upload, the decode and the status read-back, so that the read-back never waits for the training
+step queued on the consumer's stream; that stream then waits for the decode's event.  When the next batch is already
+staged as a batch is handed out, its upload and decode are issued right then (one batch ahead, nothing waited for), so they run
+under the training step and the next ``__next__`` should find the status there (measured, README: it still waits 4 to 5 ms
+per batch, against 1.3 to 2.9 ms of the threaded PIL route -- the decode call is slower under the step).  A file the decoder does not take
+(progressive, 4:2:2, ...) is decoded by PIL in the pool, as on the other routes.  The resample of an image without annotations
+reads that image's file on the drawing thread (the other routes decode it there) and it is decoded on the GPU with its batch.
 """
 import threading
 import weakref
@@ -50,11 +63,15 @@ MAX_WORKERS = 16
 _RAW_KEYS = ('raw', 'scale', 'flip', 'keep_ratio', 'img_meta', 'aug_plan')
 
 
-def draw_train_raw(dataset, idx, img=None):
+def draw_train_raw(dataset, idx, img=None, load=None):
     """``dataset[idx]``'s loop around ``prepare_train_raw``: the sample's draws, and for an image without annotations
     (``skip_img_without_anno``) the resample of ``__getitem__`` -- ``np.random.choice`` within the aspect-ratio group, then
-    that image decoded here.  ``img``: the decoded image of ``idx`` when somebody decoded it ahead."""
+    that image decoded here.  ``img``: the decoded image of ``idx`` when somebody decoded it ahead.  ``load``: what reads an
+    image nobody read ahead (``dataset.load_image_file`` on the ``device_decode`` route, so that a resampled image travels as
+    its file too; default: ``prepare_train_raw``'s own ``load_image``)."""
     while True:
+        if img is None and load is not None:
+            img = load(idx)
         raw = dataset.prepare_train_raw(idx, img=img)
         if raw is not None:
             return raw
@@ -91,16 +108,30 @@ class _Staged(object):
     """one finished batch on the host: ``block`` (uint8: the packed ground truth and, on the host route, the collated
     image behind it), its layout, and what stays on the host"""
 
-    def __init__(self, block, entries, nbytes, img_at, img_shape, metas, samples):
+    def __init__(self, block, entries, nbytes, img_at, img_shape, metas, samples, files_at=None, places=None):
         self.block, self.entries, self.nbytes = block, entries, nbytes
         self.img_at, self.img_shape, self.metas, self.samples = img_at, img_shape, metas, samples
+        self.files_at, self.places = files_at, places      # device_decode: the files' bytes in the block (jpeg.pack_files)
 
 
-def _stage(samples, raw_route, slot_block):
+def _encoded(samples):
+    """the files of a batch the device decodes: (bytes, frame) of every ``EncodedImage`` that has a frame, in order"""
+    raws = [s['raw'] for s in samples]
+    keep = [r for r in raws if isinstance(r, ds.EncodedImage) and r.frame is not None]
+    return [r.data for r in keep], [r.frame for r in keep]
+
+
+def _stage(samples, raw_route, slot_block, decode=False):
     """pack a batch for upload (host memory only): into ``slot_block`` when it is large enough, else into a pageable block of
-    the same layout, which the consumer moves into a slot it has grown"""
+    the same layout, which the consumer moves into a slot it has grown.  ``decode``: the files' bytes follow the ground truth"""
     entries, gt_bytes = gt_layout(samples)
-    if raw_route:
+    files_at = places = None
+    if raw_route and decode:
+        from . import jpeg
+        files, frames = _encoded(samples)
+        img_at, img_shape, files_at = None, None, _align(gt_bytes, 256)
+        total = files_at + jpeg.pack_files(files, frames)[0]
+    elif raw_route:
         img_at, img_shape, total = None, None, gt_bytes
     else:
         H = max(s['img'].shape[1] for s in samples)
@@ -118,7 +149,10 @@ def _stage(samples, raw_route, slot_block):
         img.zero_()
         for i, s in enumerate(samples):
             img[i, :, :s['img'].shape[1], :s['img'].shape[2]] = s['img']
-    return _Staged(block, entries, total, img_at, img_shape, [s['img_meta'] for s in samples], samples if raw_route else None)
+    if files_at is not None:
+        _, places = jpeg.pack_files(files, frames, block.numpy()[files_at:total])
+    return _Staged(block, entries, total, img_at, img_shape, [s['img_meta'] for s in samples], samples if raw_route else None,
+                   files_at, places)
 
 
 class _Epoch(object):
@@ -128,6 +162,8 @@ class _Epoch(object):
     def __init__(self, loader, order):
         self.dataset, self.B, self.prefetch = loader.dataset, loader.batch_size, max(loader.prefetch, 1)
         self.workers, self.raw_route, self.staged = loader.workers, loader.device_preprocess, loader.device is not None
+        self.decode = loader.device_decode
+        self.load = loader.dataset.load_image_file if self.decode else loader.dataset.load_image
         self.slots = loader._slots
         self.order = order
         self.n_batches = -(-len(order) // self.B)
@@ -154,7 +190,7 @@ class _Epoch(object):
         limit = min(len(self.order), (self.consumed + self.prefetch) * self.B + self.workers)
         while self.next_decode < limit and not self.stop:
             p = self.next_decode
-            self.decodes[p] = self.pool.submit(self.dataset.load_image, self.order[p])
+            self.decodes[p] = self.pool.submit(self.load, self.order[p])
             self.next_decode += 1
 
     def _produce(self):
@@ -174,7 +210,7 @@ class _Epoch(object):
                         if self.stop:
                             return
                         fut = self.decodes.pop(p)
-                    raw = draw_train_raw(self.dataset, self.order[p], fut.result())
+                    raw = draw_train_raw(self.dataset, self.order[p], fut.result(), self.load if self.decode else None)
                     futures.append(raw if self.raw_route else self.pool.submit(ds.finish_train_sample, self.dataset, raw))
                 self.pool.submit(self._assemble, k, futures)
                 with self.cv:
@@ -191,7 +227,7 @@ class _Epoch(object):
             samples = futures if self.raw_route else [f.result() for f in futures]
             if self.staged:
                 slot = self.slots[k % len(self.slots)]
-                value = _stage(samples, self.raw_route, slot.block)
+                value = _stage(samples, self.raw_route, slot.block, self.decode)
             else:
                 value = samples if self.raw_route else ds.collate(samples)
             self._publish(k, 'ok', value)
@@ -215,6 +251,13 @@ class _Epoch(object):
         if kind == 'error':
             raise value
         raise StopIteration
+
+    def take_if_ready(self, k):
+        """batch ``k`` if it is finished and sound, without waiting (else None: ``take`` will wait for it or raise its error)"""
+        with self.cv:
+            if k in self.done and self.done[k][0] == 'ok' and not self.stop:
+                return self.done.pop(k)[1]
+        return None
 
     def came_back(self):
         with self.cv:
@@ -247,7 +290,7 @@ class _Slot(object):
 
 class _LoaderIter(object):
     def __init__(self, loader, order):
-        self.loader, self.k = loader, 0
+        self.loader, self.k, self.begun = loader, 0, None
         self.epoch = _Epoch(loader, order)
         loader._active = weakref.ref(self.epoch)
 
@@ -263,9 +306,21 @@ class _LoaderIter(object):
             if old is not None and old.event is not None:
                 old.event.synchronize()
             ep.came_back()
-        value = ep.take(k)
-        if ep.staged:
-            value = loader._upload(value, loader._slots[k % len(loader._slots)])
+        if self.begun is not None:             # device_decode: this batch's decode was issued while the last one was in use
+            begun, self.begun = self.begun, None
+        else:
+            begun = ep.take(k)
+            if ep.staged:
+                begun = loader._begin_upload(begun, loader._slots[k % len(loader._slots)])
+        try:
+            value = loader._end_upload(begun) if ep.staged else begun
+            if ep.decode:
+                nxt = ep.take_if_ready(k + 1)
+                if nxt is not None:            # (its slot last sent batch k - 3 or an earlier one: synchronised above)
+                    self.begun = loader._begin_upload(nxt, loader._slots[(k + 1) % len(loader._slots)])
+        except BaseException:                  # (PIL's error for a file the device refused: the epoch ends as in ``take``)
+            ep.close()
+            raise
         self.k = k + 1
         return value
 
@@ -283,14 +338,20 @@ class DataLoader(object):
     """what ``build_dataloader`` returns: iterate it once per epoch (``Runner.run(loader, ..., set_epoch=loader.set_epoch)``);
     the module docstring states what it yields and guarantees"""
 
-    def __init__(self, dataset, batch_size, workers, sampler=None, device=None, device_preprocess=False, prefetch=2):
+    def __init__(self, dataset, batch_size, workers, sampler=None, device=None, device_preprocess=False, prefetch=2,
+                 device_decode=False):
         if workers < 0 or prefetch < 0 or batch_size < 1:
             raise ValueError('workers and prefetch are >= 0 and the batch size >= 1, got %r, %r, %r'
                              % (workers, prefetch, batch_size))
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
         self.workers = min(int(workers), MAX_WORKERS)      # a thread count, never sized from the machine
         self.prefetch, self.device_preprocess = int(prefetch), bool(device_preprocess)
-        self.device = None
+        self.device_decode = bool(device_decode)
+        if self.device_decode and not (self.device_preprocess and device is not None):
+            raise ValueError('device_decode=True needs device_preprocess=True and a device: the decoded images stay on the GPU')
+        if self.device_decode and self.batch_size > 32:
+            raise ValueError('device_decode=True decodes a batch in one call of at most 32 images, got %d' % self.batch_size)
+        self.device, self._route = None, None
         self._active = lambda: None
         self._slots, self._transform = [], None
         if device is not None:
@@ -304,6 +365,9 @@ class DataLoader(object):
             self._slots = [_Slot() for _ in range(max(self.prefetch, 1) + 2)]
             if self.device_preprocess:
                 self._transform = dataset.device_transform(self.device)
+            if self.device_decode:
+                from .jpeg import DeviceDecodeRoute
+                self._route = DeviceDecodeRoute(self.device)
 
     def __len__(self):
         n = len(self.dataset) if self.sampler is None else len(self.sampler)
@@ -345,7 +409,7 @@ class DataLoader(object):
         B, data = self.batch_size, self.dataset
         for lo in range(0, len(order), B):
             if self.device_preprocess:
-                samples = [draw_train_raw(data, i) for i in order[lo:lo + B]]
+                samples = [draw_train_raw(data, i, None, data.load_image_file if self.device_decode else None) for i in order[lo:lo + B]]
                 if self.device is None:
                     yield samples
                     continue
@@ -355,7 +419,7 @@ class DataLoader(object):
                     yield ds.collate(samples)
                     continue
             slot = _Slot()                 # nothing runs ahead: a buffer per batch, kept alive by the caching host allocator
-            yield self._upload(_stage(samples, self.device_preprocess, None), slot)
+            yield self._upload(_stage(samples, self.device_preprocess, None, self.device_decode), slot)
 
     # ---- consumer-side GPU work ------------------------------------------------------------------
     def _presize(self):
@@ -375,6 +439,11 @@ class DataLoader(object):
     def _upload(self, staged, slot):
         """one non-blocking copy of the staged block out of page-locked memory on the current stream of ``device``, the event
         behind it recorded in ``slot``; the batch dict with device views (``img`` through ``collate_device`` on the raw route)"""
+        return self._end_upload(self._begin_upload(staged, slot))
+
+    def _begin_upload(self, staged, slot):
+        """the first half of ``_upload``: everything that waits for nothing.  On the ``device_decode`` route that is the block's
+        upload, the decode and the status read-back, issued on the route's stream; on the others it is all of ``_upload``"""
         with torch.cuda.device(self.device):
             if staged.block is not slot.block:        # the slot was too small (or absent): grow it here, on the consumer
                 if slot.event is not None:
@@ -382,20 +451,40 @@ class DataLoader(object):
                 if slot.block is None or slot.block.numel() < staged.nbytes:
                     slot.block = torch.empty(_align(staged.nbytes + staged.nbytes // 4, 4096), dtype=torch.uint8, pin_memory=True)
                 slot.block[:staged.nbytes].copy_(staged.block[:staged.nbytes])
-            dev = slot.block[:staged.nbytes].to(self.device, non_blocking=True)
-            slot.event = torch.cuda.Event()
-            slot.event.record()
-            if staged.samples is not None:
-                out = dict(img=ds.collate_device(staged.samples, self._transform)['img'], img_meta=staged.metas)
+            if staged.files_at is not None:           # device_decode: upload, decode and status on the route's own stream
+                pending = self._route.start_block(slot.block[:staged.nbytes], staged.files_at, staged.places,
+                                                  [s['raw'] for s in staged.samples])
+                slot.event = pending.uploaded
+                return staged, pending
             else:
-                out = dict(img=_view(dev, staged.img_shape, torch.float32, staged.img_at), img_meta=staged.metas)
+                dev = slot.block[:staged.nbytes].to(self.device, non_blocking=True)
+                slot.event = torch.cuda.Event()
+                slot.event.record()
+                if staged.samples is not None:
+                    out = dict(img=ds.collate_device(staged.samples, self._transform)['img'], img_meta=staged.metas)
+                else:
+                    out = dict(img=_view(dev, staged.img_shape, torch.float32, staged.img_at), img_meta=staged.metas)
+            for key, shape, dtype, off in staged.entries:
+                out.setdefault(key, []).append(_view(dev, shape, dtype, off))
+        return out
+
+    def _end_upload(self, begun):
+        """the second half: the batch dict.  ``device_decode``: waits for the decode's event alone (the status), then the
+        preprocess launch on the current stream"""
+        if not isinstance(begun, tuple):
+            return begun
+        staged, pending = begun
+        with torch.cuda.device(self.device):
+            dev, raws = self._route.finish_block(pending)
+            samples = [dict(s, raw=r) for s, r in zip(staged.samples, raws)]
+            out = dict(img=ds.collate_device(samples, self._transform)['img'], img_meta=staged.metas)
             for key, shape, dtype, off in staged.entries:
                 out.setdefault(key, []).append(_view(dev, shape, dtype, off))
         return out
 
 
 def build_dataloader(dataset, imgs_per_gpu, workers_per_gpu, num_gpus=1, dist=False, shuffle=True, *, device=None,
-                     device_preprocess=False, prefetch=2, sampler=None):
+                     device_preprocess=False, prefetch=2, sampler=None, device_decode=False):
     """``mmdet.datasets.build_dataloader`` for one process.  ``shuffle=True``: ``GroupSampler`` (``dist=False``; batches of
     ``num_gpus * imgs_per_gpu``) or ``DistributedGroupSampler`` (``dist=True``); ``shuffle=False``: dataset order (this rank's
     ``runner.test_shard`` with ``dist=True``); ``sampler``: any iterable of indices with a ``len`` instead.  ``workers_per_gpu``:
@@ -404,7 +493,9 @@ def build_dataloader(dataset, imgs_per_gpu, workers_per_gpu, num_gpus=1, dist=Fa
     batch -- with ``device_preprocess=True`` the list of ``prepare_train_raw`` samples ``datasets.collate_device`` takes --;
     ``device='cuda[:n]'`` yields the batch dict on the GPU (``model(**data)``, ``GraphedTrainStep.load``): the ground truth as
     views of ONE uploaded block, ``img`` from ``collate_device`` (one launch) or, on the host route, from the same page-locked
-    block; ``img_meta`` stays a host list.  The determinism, lookahead, failure and threading contracts: the module docstring."""
+    block; ``img_meta`` stays a host list.  ``device_decode=True`` (needs ``device_preprocess=True`` and a ``device``, else
+    ``ValueError``): the JPEG files are decoded on the GPU too, the same batches bit for bit.  The determinism, lookahead,
+    failure and threading contracts: the module docstring."""
     if workers_per_gpu < 0 or prefetch < 0:
         raise ValueError('workers_per_gpu and prefetch are >= 0, got %r and %r' % (workers_per_gpu, prefetch))
     if dist:
@@ -420,4 +511,4 @@ def build_dataloader(dataset, imgs_per_gpu, workers_per_gpu, num_gpus=1, dist=Fa
             on = td.is_available() and td.is_initialized()
             sampler = test_shard(len(dataset), td.get_world_size() if on else 1, td.get_rank() if on else 0)
     return DataLoader(dataset, batch_size, workers, sampler=sampler, device=device, device_preprocess=device_preprocess,
-                      prefetch=prefetch)
+                      prefetch=prefetch, device_decode=device_decode)

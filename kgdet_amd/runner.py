@@ -228,29 +228,37 @@ class _Prefetched(object):
 
 
 def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device_preprocess=False, sink=None, workers=0,
-             show=None):
+             show=None, device_decode=False):
     """results of the samples ``indices`` in that order.  imgs_per_gpu == 1: the reference's call, one image per forward
     (``model(return_loss=False, rescale=..., **data)``, tools/test.py:25-28); > 1: runs of consecutive samples with identical
     tensor shapes and one augmentation go through ``simple_test_batch`` together (the same per-image results: nothing in
     backbone / neck / head / decode / NMS mixes the images of a batch).  ``device_preprocess``: the input transform runs on the
     model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not used then).  ``workers`` > 0: the samples are
     prepared ahead in that many threads (``_Prefetched``) and consumed in the same order -- the same calls, the same results.
-    ``show``: a ``_Show`` that draws every group's images once its detections exist."""
+    ``show``: a ``_Show`` that draws every group's images once its detections exist.  ``device_decode`` (with
+    ``device_preprocess``): the samples carry their FILES (``dataset.load_image_file``; the threads only read and parse headers)
+    and every group is decoded on the GPU in one call (``jpeg.DeviceDecodeRoute``) -- the same pixels, the same results."""
     if workers < 0:
         raise ValueError('workers is >= 0, got %r' % (workers,))
+    if device_decode and not device_preprocess:
+        raise ValueError('device_decode=True needs device_preprocess=True: the decoded images stay on the GPU')
+    prepare = None
+    if device_decode:
+        def prepare(idx):
+            return dataset.prepare_test_raw(idx, img=dataset.load_image_file(idx))
     if workers:
-        fn = dataset.prepare_test_raw if device_preprocess else dataset.__getitem__
+        fn = (prepare or dataset.prepare_test_raw) if device_preprocess else dataset.__getitem__
         ahead = _Prefetched(fn, indices, workers)
         try:
-            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show)
+            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show, prepare)
         finally:
             ahead.close()
-    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None, show)
+    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None, show, prepare)
 
 
-def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show=None):
+def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show=None, prepare=None):
     if device_preprocess:
-        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead, show)
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead, show, prepare)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
@@ -288,26 +296,37 @@ def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device
     return results
 
 
-def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None, show=None):
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None, show=None, prepare=None):
     """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
     planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
     ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
-    tensor shapes ARE the pad shapes), one launch for all augmentations of a TTA sample (its raw image uploaded once)."""
+    tensor shapes ARE the pad shapes), one launch for all augmentations of a TTA sample (its raw image uploaded once).
+    ``prepare``: the ``device_decode`` route's ``prepare_test_raw``, whose ``raw`` is the image's file: the group's files are
+    decoded in one call before the transform."""
     model.eval()
-    transform = dataset.device_transform(next(model.parameters()).device)
+    device = next(model.parameters()).device
+    transform = dataset.device_transform(device)
+    route = None
+    if prepare is not None:
+        from .jpeg import DeviceDecodeRoute
+        route = DeviceDecodeRoute(device)
+    prepare = prepare or dataset.prepare_test_raw
     results, i = [], 0
     carried = None
     while i < len(indices):
-        data = carried if carried is not None else (dataset.prepare_test_raw(indices[i]) if ahead is None else ahead(i))
+        data = carried if carried is not None else (prepare(indices[i]) if ahead is None else ahead(i))
         carried = None
         group = [data]
         while (imgs_per_gpu > 1 and len(group) < imgs_per_gpu and i + len(group) < len(indices)
                and len(data['img_meta']) == 1):
-            nxt = dataset.prepare_test_raw(indices[i + len(group)]) if ahead is None else ahead(i + len(group))
+            nxt = prepare(indices[i + len(group)]) if ahead is None else ahead(i + len(group))
             if len(nxt['img_meta']) != 1 or nxt['img_meta'][0]['pad_shape'] != data['img_meta'][0]['pad_shape']:
                 carried = nxt
                 break
             group.append(nxt)
+        if route is not None:
+            group = [dict(g, raw=r) for g, r in zip(group, route([g['raw'] for g in group]))]
+            data = group[0]
         with torch.no_grad():
             if len(group) == 1:
                 imgs, _ = transform.separate([data['raw']] * len(data['scales']), data['scales'], data['flips'],
@@ -382,7 +401,8 @@ class _Show(object):
 
 
 def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1, device_preprocess=False,
-                    device_results=False, workers=0, show_dir=None, show_score_thr=0.3, show_ext='.jpg', show_encoder='host'):
+                    device_results=False, workers=0, show_dir=None, show_score_thr=0.3, show_ext='.jpg', show_encoder='host',
+                    device_decode=False):
     """tools/test.py:18-35 without the progress bar: one result per sample, in dataset order.  ``device_preprocess``:
     resize / normalise / flip / pad on the model's GPU from the raw pixels (``_test_on_device``; ``to_device`` is not
     used then) instead of ``dataset[i]``'s host transform; same result format and order.  ``device_results``: the
@@ -396,31 +416,39 @@ def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1
     exception is re-raised, and the threads are gone when the call returns or raises.  ``show_encoder``: 'host' -- the drawn
     pictures are downloaded and the threads encode them (PIL); 'device' -- they are encoded on the GPU (``jpeg.py``: baseline
     JPEG, quality 90, the bytes of ``jpeg.jpeg_restatement``, not PIL's), only the files come down and the threads only write;
-    it takes ``show_ext`` '.jpg' / '.jpeg' (``ValueError`` before the run)."""
+    it takes ``show_ext`` '.jpg' / '.jpeg' (``ValueError`` before the run).  ``device_decode``: the JPEG files are decoded on
+    the GPU as well (``jpeg.DeviceDecodeRoute``: every group of the loop in one call, ``workers`` then only read files); it
+    needs ``device_preprocess=True`` (``ValueError`` before the run); same results."""
+    if device_decode and not device_preprocess:
+        raise ValueError('device_decode=True needs device_preprocess=True: the decoded images stay on the GPU')
     if show_dir is None:
-        return _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, None)
+        return _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, None,
+                                device_decode)
     if not rescale:
         raise ValueError('show_dir draws on the original images: it needs rescale=True')
     show = _Show(model, dataset, show_dir, show_score_thr, show_ext, workers, show_encoder)
     failed = True
     try:
-        out = _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show)
+        out = _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show,
+                               device_decode)
         failed = False
     finally:
         show.close(failed)
     return out
 
 
-def _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show):
+def _single_gpu_test(model, dataset, rescale, to_device, imgs_per_gpu, device_preprocess, device_results, workers, show,
+                     device_decode=False):
     if not device_results:
         return _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess,
-                        workers=workers, show=show)
+                        workers=workers, show=show, device_decode=device_decode)
     target = model.module if hasattr(model, 'module') else model
     M = int(target.test_cfg.max_per_img)
     if M <= 0:
         raise NotImplementedError('device results need test_cfg.max_per_img > 0 (the rows per image)')
     sink = _RowSink(len(dataset))
-    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink, workers, show)
+    _test_on(model, dataset, list(range(len(dataset))), rescale, to_device, imgs_per_gpu, device_preprocess, sink, workers, show,
+             device_decode)
     rows = sink.rows
     if rows is None:                            # (an empty dataset)
         rows = torch.empty((0, M, 10), dtype=torch.float32, device=next(target.parameters()).device)
@@ -628,15 +656,17 @@ class Runner(object):
                  log_interval=50, logger=print, batch_processor=batch_processor, eval_config=None, on_record=None):
         """``eval_config = dict(dataset=..., interval=1, imgs_per_gpu=1, device_preprocess=False, group=None, to_device=None,
         result_types=('bbox', 'keypoints'), device=None, lazy_landmarks=None, device_accumulate=None, device_results=False,
-        workers=0)``:
+        workers=0, device_decode=False)``:
         validation after every ``interval``-th epoch (``validate``); ``lazy_landmarks`` and ``device_accumulate`` are
-        ``evaluation_device.evaluate_results``'s, ``device_results`` and ``workers`` are ``single_gpu_test``'s (``device_results``
-        with ``group`` is refused: ``multi_gpu_test`` gathers host lists).  ``on_record(mode, record)``: called with 'train' or
+        ``evaluation_device.evaluate_results``'s, ``device_results``, ``workers`` and ``device_decode`` are ``single_gpu_test``'s (``device_results``
+        and ``device_decode`` with ``group`` are refused: ``multi_gpu_test`` gathers host lists).  ``on_record(mode, record)``: called with 'train' or
         'val' and every record as it is appended to ``log_history`` (``apis.train_detector`` writes its ``.log.json`` there)."""
         self.model, self.optimizer, self.work_dir = model, optimizer, work_dir
         self.eval_config = dict(eval_config) if eval_config else None
         if self.eval_config and self.eval_config.get('device_results') and self.eval_config.get('group') is not None:
             raise ValueError('eval_config: device_results covers single_gpu_test only, not a process group')
+        if self.eval_config and self.eval_config.get('device_decode') and self.eval_config.get('group') is not None:
+            raise ValueError('eval_config: device_decode covers single_gpu_test only, not a process group')
         self._packed_gt = None
         self.lr = LrSchedule(**(lr_config or dict(policy='step', step=[])))
         self.opt_hook = DistOptimizerHook(**(optimizer_config or {}))
@@ -766,7 +796,8 @@ class Runner(object):
             if group is not None:
                 results = multi_gpu_test(self.model, dataset, group=group, **kw)
             else:
-                results = single_gpu_test(self.model, dataset, device_results=bool(cfg.get('device_results', False)), **kw)
+                results = single_gpu_test(self.model, dataset, device_results=bool(cfg.get('device_results', False)),
+                                          device_decode=bool(cfg.get('device_decode', False)), **kw)
         finally:
             self.model.train(was_training)
         if results is None:                     # (not rank 0)

@@ -1,7 +1,7 @@
 """Test a detector from a config file and a checkpoint (the reference's ``tools/test.py``), one process on one GPU.
 
     python tools/test.py CONFIG CHECKPOINT [--json_out P] [--eval bbox keypoints] [--workers N] [--imgs-per-gpu N]
-                                           [--device-preprocess] [--device-results] [--out FILE.pkl]
+                                           [--device-preprocess [--device-decode]] [--device-results] [--out FILE.pkl]
                                            [--show-dir DIR] [--show-score-thr T] [--show-encoder {host,device}]
 
 ``cfg.data.test`` goes through ``runner.single_gpu_test``: ``--workers`` threads decode and prepare the upcoming images
@@ -33,6 +33,8 @@ def parse_args(argv=None):
     parser.add_argument('--workers', type=int, default=None, help='threads that prepare upcoming images')
     parser.add_argument('--imgs-per-gpu', type=int, default=1)
     parser.add_argument('--device-preprocess', action='store_true')
+    parser.add_argument('--device-decode', action='store_true',
+                        help='decode the JPEG files on the GPU (needs --device-preprocess)')
     parser.add_argument('--device-results', action='store_true')
     parser.add_argument('--out', help='output result file (a pickle of the result list)')
     parser.add_argument('--show-dir', help='directory the drawn images are written to')
@@ -50,6 +52,8 @@ def main(argv=None):
                          % args.launcher)
     if not (args.json_out or args.eval or args.out or args.show_dir):
         raise SystemExit('nothing to do: give --json_out, --eval, --out and / or --show-dir')
+    if args.device_decode and not args.device_preprocess:
+        raise SystemExit('--device-decode needs --device-preprocess')
     if args.out is not None and not args.out.endswith(('.pkl', '.pickle')):
         raise SystemExit('The output file must be a pkl file.')
     import torch
@@ -67,7 +71,8 @@ def main(argv=None):
     results = single_gpu_test(model, dataset, rescale=True, to_device=lambda t: t.cuda(non_blocking=True),
                               imgs_per_gpu=args.imgs_per_gpu, device_preprocess=args.device_preprocess,
                               device_results=args.device_results, workers=min(workers, 16), show_dir=args.show_dir,
-                              show_score_thr=args.show_score_thr, show_encoder=args.show_encoder)
+                              show_score_thr=args.show_score_thr, show_encoder=args.show_encoder,
+                              device_decode=args.device_decode)
     if args.out:
         import pickle
         print('writing results to {}'.format(args.out))

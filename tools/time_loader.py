@@ -1,7 +1,7 @@
 """Does the feed keep up?  Training and test throughput from a directory of JPEGs, against a resident batch.
 
     python tools/time_loader.py [--images 256] [--iters 200] [--warmup 20] [--workers 2,4,8,16] [--test-workers 0,4,8,16]
-                                [--rounds 2] [--skip-train] [--skip-test] [--out FILE]
+                                [--rounds 2] [--skip-train] [--skip-test] [--legs a,d,e] [--out FILE]
 
 Image set: the records of tests/golden/demo_dataset-32.json, rendered with tests/golden/demo_cases.render_image, repeated
 under fresh ids to ``--images`` and saved as JPEG into a temporary directory (sorted by size, so the test loop finds groups).
@@ -14,10 +14,15 @@ iterations per leg after ``--warmup``, all in this process, the whole list repea
     b       the serial loop: ``collate([dataset[i] ...])`` and ``.cuda()`` between steps
     c<N>    ``build_dataloader(..., device='cuda')``, host route (pixels on the host, uploaded from page-locked memory), N threads
     d<N>    the same with ``device_preprocess=True`` (raw pixels up, one preprocess launch per batch)
+    e<N>    the same with ``device_decode=True`` as well (the files' bytes up, one decode call and one preprocess launch per
+            batch); it runs right behind d<N>, so the two alternate over the rounds
 
-each with ``data_time``, the mean seconds per iteration spent in the feed's ``next()``.  The loader has no side stream, so there
-is no with / without pair to time.  Test legs -- bf16 autocast, ``imgs_per_gpu=8``, ``device_preprocess`` and
-``device_results`` on: ``single_gpu_test`` at each ``--test-workers``, images per second.
+each with ``data_time``, the mean seconds per iteration spent in the feed's ``next()``.  ``--legs``: only the legs whose name
+begins with one of these prefixes.  Test legs -- bf16 autocast, ``imgs_per_gpu=8``, ``device_preprocess`` and
+``device_results`` on: ``single_gpu_test`` at each ``--test-workers``, images per second; at ``workers`` 0 and 4 also with
+``device_decode=True`` (``w<N>_decode``), right behind the leg without.  ``single_gpu_test`` reports no feed time, so the
+tool clocks it from outside: a test leg's ``data_time`` is the seconds per IMAGE its loop's thread spent getting samples
+(``prepare_test_raw`` inline or the wait for a prefetched one) and inside the decode route's call.
 
 MIOpen's find mode is off (``cudnn.benchmark = False``) for every leg: the image set has many padded shapes, and a find per
 new shape would be timed as feed.  Prints one JSON line (also written to ``--out``): per leg the img/s of every round, their
@@ -77,6 +82,7 @@ def main(argv=None):
     ap.add_argument('--rounds', type=int, default=2)
     ap.add_argument('--skip-train', action='store_true')
     ap.add_argument('--skip-test', action='store_true')
+    ap.add_argument('--legs', default=None, help='only the training legs whose names begin with one of these prefixes')
     ap.add_argument('--out', default=None)
     args = ap.parse_args(argv)
     import torch
@@ -101,7 +107,7 @@ def main(argv=None):
         test_set = ds.DeepFashion2Dataset(flip_ratio=0, with_label=False, test_mode=True, **common)
         out = dict(images=args.images, iters=args.iters, warmup=args.warmup, rounds=args.rounds, batch=2,
                    cpus_usable=len(os.sched_getaffinity(0)), cpus_machine=os.cpu_count(), miopen_find=False,
-                   side_stream='not built', render_s=round(time.time() - t0, 1))
+                   side_stream='the device_decode route only', render_s=round(time.time() - t0, 1))
 
         cfg = configs.kgdet_r50_fpn()
         torch.manual_seed(0)
@@ -156,6 +162,11 @@ def main(argv=None):
             for w in workers:
                 legs.append(('d%d' % w, lambda w=w: epochs(build_dataloader(train_set, 2, w, device=device,
                                                                             device_preprocess=True))))
+                legs.append(('e%d' % w, lambda w=w: epochs(build_dataloader(train_set, 2, w, device=device,
+                                                                            device_preprocess=True, device_decode=True))))
+            if args.legs:
+                wanted = tuple(p for p in args.legs.split(',') if p)
+                legs = [leg for leg in legs if leg[0] == 'a' or leg[0].startswith(wanted)]
             train = {name: dict(img_s=[], data_time=[]) for name, _ in legs}
             for _ in range(args.rounds):
                 for name, make in legs:
@@ -172,31 +183,60 @@ def main(argv=None):
                 rec['spread'] = round((max(rec['img_s']) - min(rec['img_s'])) / rec['mean'], 4)
             for name, rec in train.items():
                 rec['vs_a'] = round(rec['mean'] / train['a']['mean'], 3)
-                rec['vs_a_real'] = round(rec['mean'] / train['a_real']['mean'], 3)
+                if 'a_real' in train:
+                    rec['vs_a_real'] = round(rec['mean'] / train['a_real']['mean'], 3)
             out['train'] = train
             del optimizer, hook, resident, synth
 
         if not args.skip_test:
             model.eval()
             test_workers = [int(w) for w in args.test_workers.split(',') if w]
-            test = {'w%d' % w: dict(img_s=[]) for w in test_workers}
+            test_legs = [(w, decode) for w in test_workers for decode in ((False, True) if w in (0, 4) else (False,))]
+            test = {'w%d%s' % (w, '_decode' if decode else ''): dict(img_s=[], data_time=[]) for w, decode in test_legs}
 
-            def test_run(w, dataset):
+            # ``single_gpu_test`` reports no feed time of its own, so the tool clocks the calls its loop makes for samples ON THE
+            # LOOP'S THREAD: ``prepare_test_raw`` / ``load_image_file`` inline (workers 0), the wait for a prefetched sample, and
+            # the decode route's call (upload, decode, status read-back, PIL for a refused file)
+            import threading
+            from kgdet_amd import jpeg
+            loop_thread, fed = threading.get_ident(), [0.0]
+
+            def clocked(fn):
+                def inner(*a, **kw):
+                    if threading.get_ident() != loop_thread:
+                        return fn(*a, **kw)
+                    t = time.time()
+                    try:
+                        return fn(*a, **kw)
+                    finally:
+                        fed[0] += time.time() - t
+                return inner
+
+            test_set.prepare_test_raw = clocked(test_set.prepare_test_raw)
+            test_set.load_image_file = clocked(test_set.load_image_file)
+            rn._Prefetched.__call__ = clocked(rn._Prefetched.__call__)
+            jpeg.DeviceDecodeRoute.__call__ = clocked(jpeg.DeviceDecodeRoute.__call__)
+
+            def test_run(w, dataset, decode=False):
                 with torch.autocast('cuda', dtype=torch.bfloat16):
                     res = rn.single_gpu_test(model, dataset, imgs_per_gpu=8, device_preprocess=True, device_results=True,
-                                             workers=w)
+                                             workers=w, device_decode=decode)
                 torch.cuda.synchronize()
                 return res
 
             test_run(4, test_set)                         # warm-up: every shape of the set once
+            test_run(4, test_set, True).release()
             for _ in range(args.rounds):
-                for w in test_workers:
+                for w, decode in test_legs:
                     torch.cuda.synchronize()
-                    start = time.time()
-                    test_run(w, test_set).release()
+                    start, fed[0] = time.time(), 0.0
+                    test_run(w, test_set, decode).release()
                     rate = len(test_set) / (time.time() - start)
-                    test['w%d' % w]['img_s'].append(round(rate, 1))
-                    print('test workers=%d: %.1f img/s' % (w, rate), file=sys.stderr, flush=True)
+                    rec = test['w%d%s' % (w, '_decode' if decode else '')]
+                    rec['img_s'].append(round(rate, 1))
+                    rec['data_time'].append(round(fed[0] / len(test_set), 6))
+                    print('test workers=%d%s: %.1f img/s, data_time %.3f ms per image'
+                          % (w, ' device_decode' if decode else '', rate, fed[0] / len(test_set) * 1e3), file=sys.stderr, flush=True)
             for name, rec in test.items():
                 rec['mean'] = round(float(np.mean(rec['img_s'])), 1)
                 rec['spread'] = round((max(rec['img_s']) - min(rec['img_s'])) / rec['mean'], 4)

@@ -1,7 +1,7 @@
 """Train a detector from a config file (the reference's ``tools/train.py``), one process on one GPU.
 
     python tools/train.py CONFIG [--work_dir D] [--resume_from P] [--load_from P] [--validate] [--seed N]
-                                 [--device-preprocess]
+                                 [--device-preprocess [--device-decode]]
 
 CONFIG is one of the reference's config files, unchanged.  ``--device-preprocess`` feeds the raw pixels to the GPU's input
 transform (``loader = dict(device_preprocess=True)``); without it the host pixels go up from page-locked memory.  Checkpoints
@@ -25,6 +25,8 @@ def parse_args(argv=None):
     parser.add_argument('--validate', action='store_true', help='evaluate cfg.data.val after every epoch')
     parser.add_argument('--seed', type=int, default=None, help='random seed')
     parser.add_argument('--device-preprocess', action='store_true', help='input transform on the GPU from the raw pixels')
+    parser.add_argument('--device-decode', action='store_true',
+                        help='decode the JPEG files on the GPU too (needs --device-preprocess)')
     parser.add_argument('--launcher', default='none', help='job launcher (only "none")')
     return parser.parse_args(argv)
 
@@ -47,8 +49,12 @@ def main(argv=None):
         cfg.resume_from = args.resume_from
     if args.load_from is not None:
         cfg.load_from = args.load_from
+    if args.device_decode and not args.device_preprocess:
+        raise SystemExit('--device-decode needs --device-preprocess')
     if args.device_preprocess:
         cfg.loader = dict(cfg.get('loader') or {}, device_preprocess=True)
+    if args.device_decode:
+        cfg.loader = dict(cfg.get('loader') or {}, device_decode=True)
     cfg.gpus = 1
     if args.seed is not None:
         print('Set random seed to {}'.format(args.seed))
