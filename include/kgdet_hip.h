@@ -122,6 +122,20 @@ int kgdet_conv3x3_s2_grad_input(const void *packed_t, const float *grad_y, float
 size_t kgdet_conv3x3_s2_grad_weight_workspace_bytes(int64_t B, int32_t O, int32_t C, int32_t H, int32_t W);
 int kgdet_conv3x3_s2_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t O, int32_t C, int32_t H,
                                  int32_t W, void *workspace, size_t workspace_bytes, void *stream);
+/* Grouped 3x3 convolution, padding 1, dilation 1, stride 1 or 2 (the bottleneck's conv2 of a ResNeXt,
+ * mmdet/models/backbones/resnext.py:47-56), csrc/grouped_conv.hip: x [B, C, H, W], w [C, cpg, 3, 3] with cpg in {4, 8, 16, 32}
+ * channels per group and C / cpg groups, y [B, C, Ho, Wo], Ho = (H - 1) / stride + 1, likewise Wo.  Plain fp32 operands, one
+ * fp32 FMA chain per result, no atomics: every entry point returns the same bits for the same inputs.  The forward takes the
+ * inference epilogue y = [relu](conv + bias[c]) (bias [C] nullable).  grad_weight sums over B * Ho * Wo in a fixed order: per
+ * workgroup partials in the workspace, then one pass over them.  KGDET_E_SHAPE (nothing written) for another cpg, C % cpg != 0,
+ * a stride outside {1, 2}, a null pointer or an output that overlaps another operand; KGDET_E_WORKSPACE for a short workspace. */
+int kgdet_gconv3x3_forward(const float *x, const float *w, const float *bias, float *y, int64_t B, int32_t C, int32_t cpg,
+                           int32_t H, int32_t W, int32_t stride, int32_t relu, void *stream);
+int kgdet_gconv3x3_grad_input(const float *grad_y, const float *w, float *grad_x, int64_t B, int32_t C, int32_t cpg, int32_t H,
+                              int32_t W, int32_t stride, void *stream);
+size_t kgdet_gconv3x3_workspace_bytes(int64_t B, int32_t C, int32_t cpg, int32_t H, int32_t W, int32_t stride);
+int kgdet_gconv3x3_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t C, int32_t cpg, int32_t H,
+                               int32_t W, int32_t stride, void *workspace, size_t workspace_bytes, void *stream);
 size_t kgdet_conv1x1_grad_weight_workspace_bytes(int64_t B, int32_t O, int32_t C, int64_t HW);
 int kgdet_conv1x1_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t O, int32_t C,
                               int64_t HW, void *workspace, size_t workspace_bytes, void *stream);

@@ -1,9 +1,10 @@
-"""ResNet backbone (plain PyTorch-ROCm convolutions; MIOpen supplies the MFMA kernels).
+"""ResNet and ResNeXt backbones.
 
 Mirrors mmdet/models/backbones/resnet.py: ``BasicBlock`` :13-83, ``Bottleneck`` :86-265 (including
 the optional deformable ``conv2`` + ``conv2_offset`` of the dcn configs, :162-186, 231-238),
-``make_res_layer`` :268-328, ``ResNet`` :331-525.  Parameter names follow the checkpoint-key
-contract (``conv1``, ``bn1``, ``layer{1..4}.{i}.conv{1,2,3}|bn{1,2,3}|downsample.{0,1}``).
+``make_res_layer`` :268-328, ``ResNet`` :331-525, and mmdet/models/backbones/resnext.py: the bottleneck of ``width =
+floor(planes * base_width / 64) * groups`` channels with a grouped ``conv2`` (kgdet_amd/grouped_conv.py).  Parameter names
+follow the checkpoint-key contract (``conv1``, ``bn1``, ``layer{1..4}.{i}.conv{1,2,3}|bn{1,2,3}|downsample.{0,1}``).
 BatchNorm stays in eval mode (``norm_eval``) and ``frozen_stages`` freezes the stem + first stages.
 """
 import collections
@@ -15,7 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from . import _lib, conv1x1
+from . import _lib, conv1x1, grouped_conv
 from . import dcn as dcn_ops
 from .layers import build_conv_layer, build_norm_layer, constant_init, kaiming_init
 from .registry import BACKBONES
@@ -543,6 +544,9 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
             return out
         if conv1x1.applicable_stride2(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups):
             return frozen_bn_act(conv1x1.conv3x3_stride2(x, conv.weight), bn, residual, relu)
+        if conv.groups > 1 and grouped_conv.applicable(x, conv.weight, conv.stride, conv.padding, conv.dilation, conv.groups):
+            # a ResNeXt's conv2 (the caller's gate links stay unused, as for the stride-2 route above: every node masks its own)
+            return frozen_bn_act(grouped_conv.conv3x3(x, conv.weight, conv.stride[0]), bn, residual, relu)
         if (conv.kernel_size == (1, 1) and conv.stride == (2, 2) and conv.padding == (0, 0) and x.is_cuda
                 and x.dtype == torch.float32):
             # stride-2 1x1 (the downsample branch): a 1x1 convolution of the subsampled input.  MIOpen's fp32 strided
@@ -589,6 +593,11 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
             # bias, residual and ReLU ride on the convolution's store: no separate epilogue pass
             return conv1x1._apply(hit.packed, x, hit.weight.shape[0], taps, 1, bias, residual, relu)
         out = conv1x1._apply(hit.packed, x, hit.weight.shape[0], taps)
+    elif conv.groups > 1 and grouped_conv.applicable(x, hit.weight, conv.stride, conv.padding, conv.dilation, conv.groups):
+        # fp32 inference of a grouped conv2: the folded shift and the ReLU in the store of the grouped kernel
+        if residual is None and not raw:
+            return grouped_conv.conv3x3_bias_act(x, hit.weight, bias, conv.stride[0], relu)
+        out = grouped_conv.forward(x, hit.weight, conv.stride[0])
     else:
         out = F.conv2d(x, hit.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     if raw:     # (the stem: the caller fuses bias + ReLU with the pooling)
@@ -598,9 +607,10 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
 
 class Bottleneck(nn.Module):
     expansion = 4
+    dcn_takes_groups = False     # (the ResNeXt block hands dcn['groups'] to its deformable conv2, resnext.py:59)
 
     def __init__(self, inplanes, planes, stride=1, dilation=1, downsample=None, style='pytorch', with_cp=False,
-                 conv_cfg=None, norm_cfg=dict(type='BN'), dcn=None, gcb=None, gen_attention=None):
+                 conv_cfg=None, norm_cfg=dict(type='BN'), dcn=None, gcb=None, gen_attention=None, groups=1, base_width=4):
         super(Bottleneck, self).__init__()
         assert style in ['pytorch', 'caffe']
         assert dcn is None or isinstance(dcn, dict)
@@ -615,14 +625,16 @@ class Bottleneck(nn.Module):
         self.norm_cfg = norm_cfg
         self.dcn = dcn
         self.with_dcn = dcn is not None
+        # conv1 -> conv2 -> conv3 run at `width` channels: planes, or the ResNeXt width with conv2 in `groups` groups
+        width = planes if groups == 1 else (planes * base_width // 64) * groups
         # "pytorch": the 3x3 conv carries the stride; "caffe": the first 1x1 does
         self.conv1_stride, self.conv2_stride = (1, stride) if style == 'pytorch' else (stride, 1)
 
-        self.norm1_name, norm1 = build_norm_layer(norm_cfg, planes, postfix=1)
-        self.norm2_name, norm2 = build_norm_layer(norm_cfg, planes, postfix=2)
+        self.norm1_name, norm1 = build_norm_layer(norm_cfg, width, postfix=1)
+        self.norm2_name, norm2 = build_norm_layer(norm_cfg, width, postfix=2)
         self.norm3_name, norm3 = build_norm_layer(norm_cfg, planes * self.expansion, postfix=3)
 
-        self.conv1 = build_conv_layer(conv_cfg, inplanes, planes, kernel_size=1, stride=self.conv1_stride, bias=False)
+        self.conv1 = build_conv_layer(conv_cfg, inplanes, width, kernel_size=1, stride=self.conv1_stride, bias=False)
         self.add_module(self.norm1_name, norm1)
         fallback_on_stride = False
         self.with_modulated_dcn = False
@@ -630,19 +642,20 @@ class Bottleneck(nn.Module):
             fallback_on_stride = dcn.get('fallback_on_stride', False)
             self.with_modulated_dcn = dcn.get('modulated', False)
         if not self.with_dcn or fallback_on_stride:
-            self.conv2 = build_conv_layer(conv_cfg, planes, planes, kernel_size=3, stride=self.conv2_stride,
-                                          padding=dilation, dilation=dilation, bias=False)
+            self.conv2 = build_conv_layer(conv_cfg, width, width, kernel_size=3, stride=self.conv2_stride,
+                                          padding=dilation, dilation=dilation, groups=groups, bias=False)
         else:
             assert conv_cfg is None, 'conv_cfg must be None for DCN'
             deformable_groups = dcn.get('deformable_groups', 1)
             conv_op, offset_channels = ((dcn_ops.ModulatedDeformConv, 27) if self.with_modulated_dcn else
                                         (dcn_ops.DeformConv, 18))
-            self.conv2_offset = nn.Conv2d(planes, deformable_groups * offset_channels, kernel_size=3,
+            self.conv2_offset = nn.Conv2d(width, deformable_groups * offset_channels, kernel_size=3,
                                           stride=self.conv2_stride, padding=dilation, dilation=dilation)
-            self.conv2 = conv_op(planes, planes, kernel_size=3, stride=self.conv2_stride, padding=dilation,
-                                 dilation=dilation, deformable_groups=deformable_groups, bias=False)
+            self.conv2 = conv_op(width, width, kernel_size=3, stride=self.conv2_stride, padding=dilation,
+                                 dilation=dilation, groups=dcn.get('groups', 1) if self.dcn_takes_groups else 1,
+                                 deformable_groups=deformable_groups, bias=False)
         self.add_module(self.norm2_name, norm2)
-        self.conv3 = build_conv_layer(conv_cfg, planes, planes * self.expansion, kernel_size=1, bias=False)
+        self.conv3 = build_conv_layer(conv_cfg, width, planes * self.expansion, kernel_size=1, bias=False)
         self.add_module(self.norm3_name, norm3)
 
         self.relu = nn.ReLU(inplace=True)
@@ -718,7 +731,7 @@ class Bottleneck(nn.Module):
 
 def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', with_cp=False,
                    conv_cfg=None, norm_cfg=dict(type='BN'), dcn=None, gcb=None, gen_attention=None,
-                   gen_attention_blocks=[]):
+                   gen_attention_blocks=[], **block_kwargs):
     downsample = None
     if stride != 1 or inplanes != planes * block.expansion:
         downsample = nn.Sequential(
@@ -727,12 +740,12 @@ def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style=
         )
     layers = [block(inplanes=inplanes, planes=planes, stride=stride, dilation=dilation, downsample=downsample,
                     style=style, with_cp=with_cp, conv_cfg=conv_cfg, norm_cfg=norm_cfg, dcn=dcn, gcb=gcb,
-                    gen_attention=None)]
+                    gen_attention=None, **block_kwargs)]
     inplanes = planes * block.expansion
     for _ in range(1, blocks):
         layers.append(block(inplanes=inplanes, planes=planes, stride=1, dilation=dilation, style=style,
                             with_cp=with_cp, conv_cfg=conv_cfg, norm_cfg=norm_cfg, dcn=dcn, gcb=gcb,
-                            gen_attention=None))
+                            gen_attention=None, **block_kwargs))
     return nn.Sequential(*layers)
 
 
@@ -772,7 +785,7 @@ class ResNet(nn.Module):
             planes = 64 << stage
             layer = make_res_layer(self.block, self.inplanes, planes, num_blocks, stride=strides[stage],
                                    dilation=dilations[stage], style=style, with_cp=with_cp, conv_cfg=conv_cfg,
-                                   norm_cfg=norm_cfg, dcn=dcn if stage_with_dcn[stage] else None)
+                                   norm_cfg=norm_cfg, dcn=dcn if stage_with_dcn[stage] else None, **self._block_kwargs())
             self.inplanes = planes * self.block.expansion
             self.res_layers.append('layer%d' % (stage + 1))
             self.add_module(self.res_layers[-1], layer)
@@ -782,6 +795,10 @@ class ResNet(nn.Module):
     @property
     def norm1(self):
         return getattr(self, self.norm1_name)
+
+    def _block_kwargs(self):
+        """further keywords of every block (ResNeXt: groups, base_width)"""
+        return {}
 
     def _make_stem_layer(self):
         self.conv1 = build_conv_layer(self.conv_cfg, 3, 64, kernel_size=7, stride=2, padding=3, bias=False)
@@ -876,3 +893,27 @@ class ResNet(nn.Module):
             for m in self.modules():
                 if isinstance(m, _BatchNorm):
                     m.eval()
+
+
+class ResNeXtBottleneck(Bottleneck):
+    dcn_takes_groups = True
+
+
+@BACKBONES.register_module
+class ResNeXt(ResNet):
+    """ResNet whose bottlenecks run conv1 -> conv2 -> conv3 at ``floor(planes * base_width / 64) * groups`` channels with conv2 in
+    ``groups`` groups (mmdet/models/backbones/resnext.py; 32x4d and 64x4d are the published ones).  Same keywords, attribute and
+    state-dict names as there; everything but the block's width is ``ResNet``'s."""
+    arch_settings = {
+        50: (ResNeXtBottleneck, (3, 4, 6, 3)),
+        101: (ResNeXtBottleneck, (3, 4, 23, 3)),
+        152: (ResNeXtBottleneck, (3, 8, 36, 3))
+    }
+
+    def __init__(self, groups=1, base_width=4, **kwargs):
+        # (plain ints, set before nn.Module.__init__: ResNet.__init__ builds the stages and asks _block_kwargs for them)
+        self.__dict__.update(groups=groups, base_width=base_width)
+        super(ResNeXt, self).__init__(**kwargs)
+
+    def _block_kwargs(self):
+        return dict(groups=self.groups, base_width=self.base_width)

@@ -41,6 +41,16 @@ def kgdet_r50_fpn():
                       optimizer_config=dict(grad_clip=dict(max_norm=35, norm_type=2)))
 
 
+def kgdet_x101_fpn(groups=32, base_width=4, depth=101):
+    """kgdet_r50_fpn() on a ResNeXt backbone (the RepPoints family's X101 32x4d / 64x4d models; ``depth=50`` for small runs):
+    only the backbone dict and the name of the pretrained weights differ, the bottleneck's output widths are ResNet's"""
+    cfg = kgdet_r50_fpn()
+    cfg.model.pretrained = 'open-mmlab://resnext%d_%dx%dd' % (depth, groups, base_width)
+    cfg.model.backbone = dict(type='ResNeXt', depth=depth, groups=groups, base_width=base_width, num_stages=4,
+                              out_indices=(0, 1, 2, 3), frozen_stages=1, style='pytorch')
+    return cfg
+
+
 def reppoints_kp_r50_fpn(parallel=False, soft_nms=False):
     """model, train_cfg, test_cfg of reppoints_moment_{serial,parallel}_r50_fpn_1x-deepfashion2.py
     (BASELINE config 5; ``soft_nms=True`` swaps the test-time NMS for the soft-NMS stress variant)."""
