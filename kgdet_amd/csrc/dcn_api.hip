@@ -639,6 +639,15 @@ void place_offset_xblk(DcnFwdGroup &grp, unsigned char *table_base, size_t used,
   static const bool off = env_int("KGDET_DCN_OFFSET_XBLK", 1) == 0;   // A/B switch
   place_xblk(grp, !off, table_base, used, table_cap, false);
 }
+// test hook (kgdet_debug_dcn_offset_handover): how the last grad_offset launch of the process handed its planes over -- -1: not on the
+// tap-pair kernel; otherwise the number of its problems that read a blocked input copy (0: every plane switch through registers)
+int g_offset_handover = -1;
+void note_offset_handover(const DcnFwdGroup &grp, bool use_pair) {
+  g_offset_handover = -1;
+  if (!use_pair) return;
+  g_offset_handover = 0;
+  for (int i = 0; i < grp.n; ++i) g_offset_handover += grp.p[i].xblk != nullptr;
+}
 int launch_offset_pair(const DcnFwdGroup &grp, int G, void *workspace, int max_K, void *stream) {
   if (int rc = allow_lds<dcn_bwd_offset_pair>(kMaxLds)) return rc;
   hipLaunchKernelGGL(dcn_bwd_offset_pair, dim3(G), dim3(dcn_bwd_offset_pair_threads()), dcn_bwd_offset_pair_lds_bytes(),
@@ -1101,6 +1110,7 @@ static int grad_offset_plane(const kgdet_dcn_shape *s, const float *input, const
   }
   const bool use_pair = parts == 2 && !mask && offset_pair_ok(grp);
   if (use_pair) place_offset_xblk(grp, recs, grad_tap_bytes(s, d), workspace_bytes - slab_bytes());
+  note_offset_handover(grp, use_pair);
   hipLaunchKernelGGL(dcn_build_grad_taps, dim3(2 * G, grp.n), dim3(256), 0, (hipStream_t)stream, grp);
   const size_t lds = dcn_bwd_offset_plane_lds_bytes(parts, d.K, s->H * s->W, mask != nullptr);
   const int threads = dcn_bwd_offset_plane_threads();
@@ -1142,6 +1152,8 @@ int kgdet_debug_dcn_hot_columns(int *out, int max_out) {
   for (; w < g_hot_dbg.n_vals && w < max_out; ++w) out[w] = g_hot_dbg.vals[w];
   return w;
 }
+
+int kgdet_debug_dcn_offset_handover(void) { return g_offset_handover; }
 
 // n v1 problems: grad_input of all of them in one dcn_bwd_input_plane launch, grad_offset of all of them in one
 // dcn_bwd_offset_plane launch (inverse / gradient records are built once per distinct offset tensor).
@@ -1374,6 +1386,7 @@ int kgdet_deform_conv_backward_input_grouped(int32_t n, const kgdet_dcn_shape *c
   }
   const bool use_pair = offset_pair_ok(grp);
   if (use_pair) place_offset_xblk(grp, tab, rec_total, workspace_bytes - slab_bytes());
+  note_offset_handover(grp, use_pair);
   hipLaunchKernelGGL(dcn_build_grad_taps, dim3(2 * G, grp.n), dim3(256), 0, (hipStream_t)stream, grp);
   if (use_pair) {
     if (int rc = launch_offset_pair(grp, Go, workspace, max_K, stream)) return rc;
@@ -1565,8 +1578,15 @@ int kgdet_deform_conv_backward_input(const kgdet_dcn_shape *s, const float *inpu
   // v1 on small maps: the two plane kernels (grad_input by transposed sampling, grad_offset with the column
   // gradient in registers), bf16 hi/lo split MFMA -- 2x faster than the f32 gather kernel below
   const bool plane_off = g_options[KGDET_OPT_EXACT_BACKWARD] != 0;
-  if (!plane_off && plane_bwd_input_ok(s, d) && plane_bwd_offset_ok(s, d, mask != nullptr) &&
-      workspace_bytes >= kgdet_dcn_workspace_bytes(s)) {
+  if (!plane_off && plane_bwd_input_ok(s, d) && plane_bwd_offset_ok(s, d, mask != nullptr)) {
+    // The route is a function of the shape and the options alone, never of the room in the workspace: a buffer too short for
+    // the two plane launches is refused here, before either writes anything (a shorter buffer used to send the call down the
+    // exact-fp32 kernels below: KGDET_OK with other bits for the same call).
+    const size_t need = slab_bytes() + std::max(grad_tap_bytes(s, d), bwd_input_table_bytes(s, d));
+    if (workspace == nullptr || workspace_bytes < need) {
+      set_error("workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+      return KGDET_E_WORKSPACE;
+    }
     // (grad_offset first: the v2 variant declines -- before launching anything -- when its ranges outnumber the
     // workgroups, and the gather path below then does everything)
     const int rc = grad_offset_plane(s, input, offset, mask, packed_weight, grad_output, grad_offset, grad_mask, 0, workspace,
@@ -1670,7 +1690,9 @@ int kgdet_deform_conv_backward_weight(const kgdet_dcn_shape *s, const float *inp
     const int rc = grad_weight_plane_grouped(1, &s, &input, &offset, mask ? &mask : nullptr, &grad_output, &grad_weight, workspace,
                                              workspace_bytes, stream, !plane_ok(s, d));
     if (rc == KGDET_OK) return launch_bias_grad(s, d, grad_output, grad_bias, accumulate, stream);
-    if (rc != KGDET_E_UNSUPPORTED && rc != KGDET_E_WORKSPACE) return rc;   // else: the f32 kernel below
+    // (KGDET_E_WORKSPACE is returned as it is: falling through to the f32 kernel, which needs less, gave a short buffer
+    // KGDET_OK with another summation order than the same call on the queried size)
+    if (rc != KGDET_E_UNSUPPORTED) return rc;   // else: the f32 kernel below
   }
   const int cpdg = s->C / s->deformable_groups;
   if (!(s->deformable_groups == 1 || cpdg % d.Cg == 0 || (d.Cg % cpdg == 0 && cpdg % kTileN == 0))) {

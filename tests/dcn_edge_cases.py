@@ -25,7 +25,7 @@ E = 2.0 ** -10
 # the shapes of tests/test_dcn_edge_cases.py and tests/test_gpu_dcn_edges.py, and what each is there for
 CASES = [
     # N, C, H, W, O, k, stride, pad, dil, groups, dg
-    (2, 16, 6, 7, 32, 3, 1, 1, 1, 1, 1),      # plane kernels; O % 32 == 0, unmasked: grad_offset on the tap-pair kernel
+    (2, 16, 6, 7, 32, 3, 1, 1, 1, 1, 1),      # plane kernels; O % 32 == 0, but one chunk per tap: no static schedule, dcn_bwd_offset_plane<2>
     (2, 16, 6, 7, 16, 3, 1, 1, 1, 1, 1),      # O = 16: grad_offset on dcn_bwd_offset_plane<2>; masked: its v2 variant
     (2, 6, 6, 7, 10, 3, 1, 1, 1, 1, 1),       # channel counts inside one 16-chunk, padded rows
     (2, 16, 5, 2, 16, 3, 1, 1, 1, 1, 1),      # W == 2: both end branches of make_tap_pair on one column pair
@@ -35,6 +35,9 @@ CASES = [
     (1, 16, 7, 6, 16, 7, 1, 3, 1, 1, 1),      # 7x7 taps (K = 49)
     (1, 16, 38, 36, 16, 3, 1, 1, 1, 1, 1),    # 1 368 pixels, above the LDS plane (1 344): gather forward, large-map backward
     (1, 32, 38, 36, 32, 3, 1, 1, 1, 2, 2),    # the same with weight groups and deformable groups
+    # two chunks per tap, O % 32 == 0: the fewest channels at which plan_static_ranges gives grad_offset its static schedule (two
+    # tiles of 18 stages on two workgroups; with 16 channels the two tiles meet ONE workgroup), i.e. the tap-pair kernel
+    (2, 32, 6, 7, 32, 3, 1, 1, 1, 1, 1),      # unmasked: grad_offset on dcn_bwd_offset_pair, blocked input copy or registers
 ]
 SMALL_CASES = [c for c in CASES if c[2] * c[3] <= 1344]
 LARGE_CASES = [c for c in CASES if c[2] * c[3] > 1344]

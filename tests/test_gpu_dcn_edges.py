@@ -10,8 +10,10 @@ Which kernel serves which shape (csrc/dcn_api.hip; HW = H * W of the input map, 
   forward 'split' / 'bf16'   plane_ok (HW <= 1344): dcn_fwd_plane<2> / <1>;  else gather_ok: dcn_fwd_gather<2> / <1>
   forward 'exact'            always dcn_fwd_mfma (make_tap_pair, needs W >= 2)
   backward, default          HW <= 1344, plane_bwd_input_ok and plane_bwd_offset_ok: dcn_bwd_input_plane<2> (inverse records of
-                             dcn_build_inverse_taps, overflow sums) + grad_offset on dcn_bwd_offset_pair (v1, Og % 32 == 0, K >= 3),
-                             dcn_bwd_offset_plane<2> (v1 otherwise) or dcn_bwd_offset_plane_masked (v2), records of dcn_build_grad_taps;
+                             dcn_build_inverse_taps, overflow sums) + grad_offset on dcn_bwd_offset_pair (v1, Og % 32 == 0, K >= 3 and
+                             the static schedule of plan_static_ranges: of these shapes only 2x32x6x7x32 -- with 16 channels the two
+                             pixel tiles share one workgroup and run stream-K), dcn_bwd_offset_plane<2> (v1 otherwise) or
+                             dcn_bwd_offset_plane_masked (v2), records of dcn_build_grad_taps;
                              grad_weight on dcn_bwd_weight_os<2> (all tiles in one round) or dcn_bwd_weight_plane<2> (stream-K option);
                              HW > 1344: dcn_backward_large.hip per channel run + dcn_bwd_weight_gather<2>
   backward, 'exact'          HW <= 1088 (plan_bwd_lds): dcn_bwd_build_index + dcn_bwd_input_gather (dcn_backward_gather.hip);
@@ -123,7 +125,7 @@ def test_backward_default_arithmetic(case, kind):
     """Autograd backward, v1 and v2, default (split-operand) arithmetic, twice with identical bits.  Maps of at most 1344 pixels
     (plane_bwd_input_ok, plane_bwd_offset_ok): grad_input on dcn_bwd_input_plane<2> from the inverse records -- the short palette on
     small maps sends dozens of contributions into every border cell, through the more-than-8-entry overflow records --, grad_offset
-    on the tap-pair kernel (v1, O % 32 == 0), dcn_bwd_offset_plane<2> (v1, O = 16 / 10) or dcn_bwd_offset_plane_masked (v2, where a
+    on the tap-pair kernel (v1, 2x32x6x7x32), dcn_bwd_offset_plane<2> (v1, the others) or dcn_bwd_offset_plane_masked (v2, where a
     mask of exactly 0 must not kill grad_mask), grad_weight on the plane kernel.  38 x 36: dcn_backward_large.hip (inverse index per
     channel run) and dcn_bwd_weight_gather<2>."""
     _require_gpu()
@@ -151,7 +153,7 @@ assert GRAD_INPUT_CASES == GRAD_OFFSET_CASES == GRAD_WEIGHT_CASES == E.SMALL_CAS
 @pytest.mark.parametrize('case', E.SMALL_CASES, ids=E.case_id)
 def test_plane_entry_points_directly(case):
     """dcn.grad_input_plane (v1 and masked), dcn.grad_offset_plane and dcn.grad_weights_grouped decline instead of falling back, so a
-    pass means the plane kernel computed the result: dcn_bwd_input_plane<2>; dcn_bwd_offset_pair for O % 32 == 0 and
+    pass means the plane kernel computed the result: dcn_bwd_input_plane<2>; dcn_bwd_offset_pair for 2x32x6x7x32 and
     dcn_bwd_offset_plane<2> otherwise (offset_pair_ok); dcn_bwd_weight_os<2>, and dcn_bwd_weight_plane<2> under the stream-K option."""
     _require_gpu()
     from kgdet_amd import _lib, dcn

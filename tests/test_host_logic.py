@@ -475,6 +475,58 @@ def test_nms_workspace_bound_covers_every_split():
         assert got >= need, (lengths[:5], len(lengths), got, need)
 
 
+def test_dcn_workspace_queries_are_consistent():
+    """kgdet_dcn_workspace_bytes / kgdet_dcn_group_workspace_bytes / kgdet_dcn_packed_weight_bytes (csrc/dcn_api.hip) are host
+    arithmetic: over N in {1, 2, 8}, the shapes of tests/dcn_edge_cases.py and the head's shapes (C = O = 256, 3x3 / 5x5 / 7x7, the
+    five pyramid levels of an 800 x 1333 input, groups / deformable groups in {1, 2}) the group query covers every member's single
+    query and grows with every problem added, a single query is positive exactly when kgdet_dcn_output_size accepts the shape, and
+    the packed weight's size depends on the weight alone (the comment on split_images_ok: one pack serves every pyramid level and
+    batch size)."""
+    import ctypes
+    from kgdet_amd import _lib
+    from tests import dcn_edge_cases as E
+    L = _lib.lib()
+
+    def shape(N, C, H, W, O, k, s, p, d, g, dg):
+        return _lib.DcnShape(N, C, H, W, O, k, k, s, s, p, p, d, d, g, dg, 0, 0)
+    single = lambda s: L.kgdet_dcn_workspace_bytes(ctypes.byref(s))
+
+    def group(shapes):
+        arr = (ctypes.POINTER(_lib.DcnShape) * len(shapes))(*[ctypes.pointer(s) for s in shapes])
+        return L.kgdet_dcn_group_workspace_bytes(len(shapes), arr)
+    levels = [(-(-800 // st), -(-1344 // st)) for st in (8, 16, 32, 64, 128)]      # 800 x 1333 padded to a multiple of 32
+    assert levels[0] == (100, 168) and levels[-1] == (7, 11)
+    head = [(1, 256, H, W, 256, k, 1, k // 2, 1, g, dg) for H, W in levels for k in (3, 5, 7) for g in (1, 2) for dg in (1, 2)]
+    packed = {}
+    for N in (1, 2, 8):
+        shapes = [shape(N, *c[1:]) for c in list(E.CASES) + head]
+        for s in shapes:
+            ok = L.kgdet_dcn_output_size(ctypes.byref(s), None, None) == _lib.KGDET_OK
+            assert ok and single(s) > 0, ('a valid shape without a workspace size', N, s.C, s.H, s.W, s.kh)
+            key = (s.C, s.O, s.kh, s.groups, s.deformable_groups)
+            nbytes = L.kgdet_dcn_packed_weight_bytes(ctypes.byref(s))
+            assert nbytes > 0 and packed.setdefault(key, nbytes) == nbytes, ('packed weight bytes depend on N, H or W', key, N, s.H, s.W)
+        # the stages the head launches: per level, the kernel sizes of one (groups, deformable groups) choice on two maps
+        stages = [[s for s in shapes[len(E.CASES):] if (s.H, s.groups, s.deformable_groups) == (H, g, dg)] * 2
+                  for H, _ in levels for g in (1, 2) for dg in (1, 2)]
+        stages += [shapes[:len(E.CASES)], [shape(N, 16, 6, 7, 16, k, 1, k // 2, 1, 1, 1) for k in (3, 5, 7)] * 2]
+        for members in stages:
+            assert len(members) >= 3
+            prev = 0
+            for n in range(1, len(members) + 1):
+                got = group(members[:n])
+                assert got >= max(single(s) for s in members[:n]), ('group query below a member\'s single query', N, n)
+                assert got >= prev, ('group query shrinks when a problem is added', N, n, got, prev)
+                prev = got
+    # shapes kgdet_dcn_output_size refuses: no workspace size, no packed size, and a group that holds one has none either
+    good = shape(2, 16, 6, 7, 16, 3, 1, 1, 1, 1, 1)
+    for bad in (shape(2, 16, 1, 9, 16, 7, 1, 0, 1, 1, 1), shape(2, 16, 6, 7, 16, 3, 1, 1, 4, 1, 1), shape(0, 16, 6, 7, 16, 3, 1, 1, 1, 1, 1),
+                shape(2, 16, 6, 7, 16, 3, 0, 1, 1, 1, 1), shape(2, 15, 6, 7, 16, 3, 1, 1, 1, 2, 1), shape(2, 16, 6, 7, 16, 3, 1, 1, 1, 1, 3)):
+        assert L.kgdet_dcn_output_size(ctypes.byref(bad), None, None) != _lib.KGDET_OK
+        assert single(bad) == 0 and L.kgdet_dcn_packed_weight_bytes(ctypes.byref(bad)) == 0 and group([good, bad]) == 0
+    assert single(good) > 0
+
+
 def _run_bench(argv, env_extra):
     import subprocess
     import sys
