@@ -136,6 +136,19 @@ int kgdet_gconv3x3_grad_input(const float *grad_y, const float *w, float *grad_x
 size_t kgdet_gconv3x3_workspace_bytes(int64_t B, int32_t C, int32_t cpg, int32_t H, int32_t W, int32_t stride);
 int kgdet_gconv3x3_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t C, int32_t cpg, int32_t H,
                                int32_t W, int32_t stride, void *workspace, size_t workspace_bytes, void *stream);
+/* The same convolution at bf16 inference on channels-last storage, csrc/grouped_conv_nhwc.hip: x [B, H, W, C] bf16,
+ * w [C][3][3][cpg] bf16 (the channels-last storage of a [C, cpg, 3, 3] tensor), bias fp32 [C] or NULL, y [B, Ho, Wo, C] bf16.
+ * S = the sum of the exact bf16 products in fp32 (MFMA).  bias == NULL && relu == 0: y = bf16(S), the raw output that
+ * kgdet_conv1x1_nhwc_residual_in takes with in_bias; otherwise y = bf16([relu](fp32(bf16(S)) + bias[c])), a NULL bias read as
+ * 0 -- the roundings (to nearest even) of a bf16 convolution followed by kgdet_bias_act.  cpg in {4, 8, 16, 32}, C % cpg == 0,
+ * C % 8 == 0, stride 1 or 2, B, H, W >= 1; grid limits: H, W <= 2^30, C <= 64 * 65535, B <= 2^31.  Every pointer 16-byte
+ * aligned.  At cpg 4 and 8 the groups of one aligned 16-channel block share an MFMA with zero weights across groups: a
+ * non-finite activation there reaches the block's other groups.  One launch on `stream`: no atomics, no workspace, no
+ * read-back, equal bits from call to call.  KGDET_E_SHAPE, from the host before any launch with nothing written, for another
+ * cpg or stride, C % cpg != 0, C % 8 != 0, a null x / w / y, a misaligned pointer, a size beyond the limits or a y that
+ * overlaps an operand. */
+int kgdet_gconv3x3_nhwc_bf16(const void *x, const void *w, const float *bias, void *y, int64_t B, int32_t C, int32_t cpg,
+                             int32_t H, int32_t W, int32_t stride, int32_t relu, void *stream);
 size_t kgdet_conv1x1_grad_weight_workspace_bytes(int64_t B, int32_t O, int32_t C, int64_t HW);
 int kgdet_conv1x1_grad_weight(const float *grad_y, const float *x, float *grad_w, int64_t B, int32_t O, int32_t C,
                               int64_t HW, void *workspace, size_t workspace_bytes, void *stream);

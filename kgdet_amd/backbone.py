@@ -598,6 +598,13 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
         if residual is None and not raw:
             return grouped_conv.conv3x3_bias_act(x, hit.weight, bias, conv.stride[0], relu)
         out = grouped_conv.forward(x, hit.weight, conv.stride[0])
+    elif bf16 and conv.groups > 1 and grouped_conv.applicable_bf16(x, hit.weight, conv.stride, conv.padding, conv.dilation,
+                                                                   conv.groups):
+        # bf16 inference of a grouped conv2 (opt-in, grouped_conv.BF16): raw in front of the fused conv3 kernel, else the folded
+        # shift and the ReLU in the store -- no epilogue pass
+        if residual is None and not raw:
+            return grouped_conv.conv3x3_nhwc(x, hit.weight, conv.stride[0], bias, relu)
+        out = grouped_conv.conv3x3_nhwc(x, hit.weight, conv.stride[0])
     else:
         out = F.conv2d(x, hit.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
     if raw:     # (the stem: the caller fuses bias + ReLU with the pooling)

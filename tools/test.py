@@ -3,6 +3,7 @@
     python tools/test.py CONFIG CHECKPOINT [--json_out P] [--eval bbox keypoints] [--workers N] [--imgs-per-gpu N]
                                            [--device-preprocess [--device-decode]] [--device-results] [--out FILE.pkl]
                                            [--show-dir DIR] [--show-score-thr T] [--show-encoder {host,device}]
+                                           [--grouped-bf16 {0,1,force}]
 
 ``cfg.data.test`` goes through ``runner.single_gpu_test``: ``--workers`` threads decode and prepare the upcoming images
 (default ``cfg.data.workers_per_gpu``), ``--imgs-per-gpu`` images of one shape share a forward pass, ``--device-preprocess``
@@ -14,7 +15,9 @@ those files with ``coco_eval``; without it ``--eval`` evaluates the results wher
 (the reference's ``--show``, into files): every image with its detections above ``--show-score-thr`` and their landmarks, drawn
 on the GPU a group at a time (``kgdet_draw_detections``) and encoded to ``DIR/<image file name>.jpg`` by the ``--workers``
 threads; with ``--show-encoder device`` the pictures are encoded on the GPU as well (``kgdet_jpeg_encode``: baseline JPEG at
-quality 90, other bytes than PIL's) and the threads only write the files.  A ``--launcher`` other than ``none`` is refused:
+quality 90, other bytes than PIL's) and the threads only write the files.  ``--grouped-bf16`` sets
+``kgdet_amd.grouped_conv.BF16``: the grouped conv2 of a ResNeXt backbone on the bf16 channels-last HIP kernel (``1``: the classes
+measured faster than torch's route, ``force``: all; default: ``KGDET_GROUPED_CONV_BF16``, else off).  A ``--launcher`` other than ``none`` is refused:
 the multi-rank launch is not part of this tool."""
 import argparse
 import os
@@ -41,6 +44,8 @@ def parse_args(argv=None):
     parser.add_argument('--show-score-thr', type=float, default=0.3, help='score threshold of the drawn detections')
     parser.add_argument('--show-encoder', choices=['host', 'device'], default='host',
                         help='where the drawn images become JPEG files: PIL in the writer threads, or kernels on the GPU')
+    parser.add_argument('--grouped-bf16', choices=['0', '1', 'force'], default=None,
+                        help='grouped 3x3 convolutions of a ResNeXt at bf16 inference on the HIP kernel (default: off)')
     parser.add_argument('--launcher', default='none', help='job launcher (only "none")')
     return parser.parse_args(argv)
 
@@ -63,6 +68,9 @@ def main(argv=None):
     from kgdet_amd.runner import single_gpu_test
     if not torch.cuda.is_available():
         raise SystemExit('tools/test.py needs a GPU')
+    if args.grouped_bf16 is not None:
+        from kgdet_amd import grouped_conv
+        grouped_conv.BF16 = grouped_conv.parse_bf16(args.grouped_bf16)
     cfg = Config.fromfile(args.config)
     cfg.data.test.test_mode = True
     dataset = build_dataset(cfg.data.test)

@@ -10,6 +10,15 @@ between two events per route, the two routes taking turns window by window; medi
 must move (its operands and its result once) and that traffic as a share of the 6.29 TB/s of a float4 copy.  ``--step``: one
 eager KGDet training step on the X101-32x4d model with every class on the route, with the default classes and with every
 class on torch, in turn, twice (``--nets ''`` skips the kernel table).  Prints a table and one JSON line.
+
+    python tools/time_grouped_conv.py --bf16 [--nets 32x4d,64x4d] [--batch 8] [--size 800x1344] [--step]
+
+``--bf16``: the inference route on channels-last bf16 storage (csrc/grouped_conv_nhwc.hip) at batch 8 by default.  Per shape the
+raw convolution -- ``F.conv2d`` against ``grouped_conv.conv3x3_nhwc`` -- and the convolution with shift and ReLU -- ``F.conv2d``
++ ``kgdet_bias_act`` against the route's one launch --, the routes taking turns in the same windows; the verdict per
+(channels per group, stride) class: faster only where the gap between the medians exceeds the spread (max - min) of both
+routes' windows, in both modes.  ``--bf16 --step``: one bf16 autocast ``simple_test`` of the X101-32x4d detector at that batch
+with the switch off, at ``force`` and at ``1``, in turn, twice.
 A run without a GPU fails."""
 import argparse
 import json
@@ -104,6 +113,105 @@ def time_shape(B, C, cpg, H, W, stride, windows, iters):
     return rec
 
 
+def time_shape_bf16(B, C, cpg, H, W, stride, windows, iters):
+    import torch
+    import torch.nn.functional as F
+    from kgdet_amd import backbone, grouped_conv as G
+    groups = C // cpg
+    g = torch.Generator('cuda').manual_seed(C + H)
+    cl = torch.channels_last
+    x = torch.randn(B, C, H, W, device='cuda', generator=g).to(torch.bfloat16).contiguous(memory_format=cl)
+    w = (torch.randn(C, cpg, 3, 3, device='cuda', generator=g) * 0.05).to(torch.bfloat16).contiguous(memory_format=cl)
+    bias = torch.randn(C, device='cuda', generator=g)
+    assert G.shape_ok(x.shape, w.shape, stride, 1, 1, groups) and C % 8 == 0
+
+    def torch_raw():
+        return F.conv2d(x, w, None, stride, 1, 1, groups)
+    legs = {
+        'raw': {'hip': lambda: G.conv3x3_nhwc(x, w, stride), 'torch': torch_raw},
+        'bias_relu': {'hip': lambda: G.conv3x3_nhwc(x, w, stride, bias, True),
+                      'torch': lambda: backbone._epilogue_(torch_raw(), bias, None, True)}}
+    y = torch_raw()
+    assert y.is_contiguous(memory_format=cl)
+    # the two routes agree (fp32 sums in another order, one bf16 rounding apart at the most) before anything is timed
+    for name, fns in legs.items():
+        got, want = fns['hip']().float(), fns['torch']().float()
+        assert float((got - want).abs().max()) <= 2.0 ** -6 * float(want.abs().max()), name
+    nbytes = 2 * (x.numel() + y.numel() + w.numel())
+    rec = {}
+    with torch.no_grad():
+        for name, fns in legs.items():
+            t = alternate(fns, windows, iters)
+            hip, ref = stats(t['hip']), stats(t['torch'])
+            spread = max(hip['max'] - hip['min'], ref['max'] - ref['min'])
+            rec[name] = dict(bytes=nbytes, hip_us=hip, torch_us=ref,
+                             hip_share_of_copy=round(nbytes / (np.median(t['hip']) * 1e-6) / (COPY_TB_S * 1e12), 3),
+                             torch_share_of_copy=round(nbytes / (np.median(t['torch']) * 1e-6) / (COPY_TB_S * 1e12), 3),
+                             hip_over_torch=round(float(np.median(t['hip']) / np.median(t['torch'])), 3),
+                             faster=bool(ref['median'] - hip['median'] > spread))
+    return rec
+
+
+def time_step_bf16(batch, H, W, rounds=2, iters=3):
+    """one bf16 autocast simple_test of the X101-32x4d KGDet model, switch off / force / 1 alternated ``rounds`` times: ms"""
+    import torch
+    from kgdet_amd import configs, grouped_conv as G, synthetic
+    from kgdet_amd.registry import build_detector
+    cfg = configs.kgdet_x101_fpn()
+    torch.manual_seed(0)
+    model = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).cuda()
+    model.eval()
+    data = synthetic.make_batch(batch, 'cuda', seed=0, img_shape=(H, W, 3), pad_shape=(H, W, 3))
+    auto = lambda: torch.autocast('cuda', dtype=torch.bfloat16)       # noqa: E731
+    synthetic.calibrate_scores(model, data, cfg.test_cfg.score_thr, autocast=auto())
+
+    def step():
+        with torch.no_grad(), auto():
+            model.simple_test(data['img'], data['img_meta'], rescale=True)
+    legs = ('0', 'force', '1')
+    out = {name: [] for name in legs}
+    saved = G.BF16
+    try:
+        for G.BF16 in legs:          # warm-up of every route (the measured 1x1 choices, MIOpen's algorithms)
+            for _ in range(3):
+                step()
+        for _ in range(rounds):
+            for G.BF16 in legs:
+                G.reset_calls_nhwc()
+                out[G.BF16].append(window(step, iters) / 1000.0)
+                assert (sum(G.calls_nhwc.values()) > 0) == (G.BF16 == 'force' or (G.BF16 == '1' and len(G.TORCH_CLASSES_BF16) < 8))
+    finally:
+        G.BF16 = saved
+    return {k: [round(v, 2) for v in vs] for k, vs in out.items()}
+
+
+def main_bf16(args, H, W):
+    batch = 8 if args.batch is None else args.batch
+    result = dict(bf16=True, batch=batch, size=[H, W], windows=args.windows, iters=args.iters, nets={})
+    verdict = {}
+    for net in [n for n in args.nets.split(',') if n]:
+        rows = []
+        for label, layers, B, C, cpg, h, w, stride in shapes(net, batch, H, W):
+            rec = time_shape_bf16(B, C, cpg, h, w, stride, args.windows, args.iters)
+            rows.append(dict(layer=label, layers=layers, C=C, cpg=cpg, H=h, W=w, stride=stride, **rec))
+            for name in ('raw', 'bias_relu'):
+                r = rec[name]
+                verdict.setdefault((cpg, stride), []).append(r['faster'])
+                print('%-6s %-9s x%-2d C=%4d cpg=%2d %3dx%-3d s%d %-9s hip %8.1f us (%.1f-%.1f, %.2f of copy)  torch %8.1f us '
+                      '(%.1f-%.1f, %.2f of copy)  hip/torch %.2f %s' % (
+                          net, label, layers, C, cpg, h, w, stride, name, r['hip_us']['median'], r['hip_us']['min'],
+                          r['hip_us']['max'], r['hip_share_of_copy'], r['torch_us']['median'], r['torch_us']['min'],
+                          r['torch_us']['max'], r['torch_share_of_copy'], r['hip_over_torch'],
+                          'faster' if r['faster'] else 'not faster'), flush=True)
+        result['nets'][net] = rows
+    result['torch_classes'] = sorted(k for k, v in verdict.items() if not all(v))
+    print('classes that stay on torch (not faster beyond the spread in every row):', result['torch_classes'], flush=True)
+    if args.step:
+        result['step_ms'] = time_step_bf16(batch, H, W)
+        print('bf16 simple_test, ms:', result['step_ms'], flush=True)
+    print(json.dumps(result))
+
+
 def time_step(batch, H, W, rounds=2, iters=3):
     """one eager training step of the X101-32x4d KGDet model, route on / off alternated ``rounds`` times: ms per step"""
     import torch
@@ -141,16 +249,20 @@ def time_step(batch, H, W, rounds=2, iters=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--nets', default='32x4d,64x4d')
-    ap.add_argument('--batch', type=int, default=2)
+    ap.add_argument('--batch', type=int, default=None, help='default 2, with --bf16 8')
     ap.add_argument('--size', default='800x1344')
     ap.add_argument('--windows', type=int, default=9)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--step', action='store_true')
+    ap.add_argument('--bf16', action='store_true', help='the bf16 channels-last inference route instead of the fp32 kernels')
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('time_grouped_conv: needs a GPU (nothing is measured without one)')
     H, W = (int(v) for v in args.size.split('x'))
+    if args.bf16:
+        return main_bf16(args, H, W)
+    args.batch = 2 if args.batch is None else args.batch
     result = dict(batch=args.batch, size=[H, W], windows=args.windows, iters=args.iters, nets={})
     for net in [n for n in args.nets.split(',') if n]:
         rows = []
