@@ -612,6 +612,48 @@ def _conv_bn(conv, bn, x, relu=False, residual=None, skip=False, raw=False, in_b
     return _epilogue_(out, bias, residual, relu)
 
 
+class _OffsetConvStride2(torch.autograd.Function):
+    """``F.conv2d(x, weight, bias, stride=2, padding=1)`` of a 3x3 convolution: forward, grad_input and grad_bias on torch's fp32
+    convolution as before, the weight gradient on the gather + 1x1 weight-gradient GEMM of csrc/dense_grad_weight.hip
+    (kgdet_conv3x3_s2_grad_weight: any channel counts with an even product, bf16 parts -- no envelope --, a fixed order of sums)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        ctx.save_for_backward(x, weight)
+        ctx.has_bias = bias is not None
+        return F.conv2d(x, weight, bias, 2, 1)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gy = gy.contiguous()
+        need_gx, need_gb = ctx.needs_input_grad[0], ctx.has_bias and ctx.needs_input_grad[2]
+        gx = gb = None
+        if need_gx or need_gb:
+            gx, _, gb = torch.ops.aten.convolution_backward(
+                gy, x, weight, [weight.shape[0]] if need_gb else None, [2, 2], [1, 1], [1, 1], False, [0, 0], 1,
+                [need_gx, False, need_gb])
+        gw = None
+        if ctx.needs_input_grad[1]:
+            gw = conv1x1._grad_weight_launch('kgdet_conv3x3_s2_grad_weight', x, weight.contiguous(), gy)
+        return (gx if need_gx else None), gw, (gb if need_gb else None)
+
+
+def _offset_conv(conv, x):
+    """``conv(x)`` for the biased 3x3 convolution that predicts the offsets (and masks) of a deformable conv2.  At stride 2 the
+    weight gradient of torch's convolution was seen to change its last bits from call to call on an MI355X (supposed: a split sum
+    added with float atomics inside MIOpen), and with it the gradient of ``conv2_offset.weight`` from pass to pass: that one
+    product runs on the library's kernel (_OffsetConvStride2); everything else of the convolution stays where it was.  At stride 1
+    the module is called as before (there every product repeated its bits on the shapes tried)."""
+    w = conv.weight
+    if (type(conv) is nn.Conv2d and conv1x1.ENABLED and torch.is_grad_enabled() and w.requires_grad and x.is_cuda
+            and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 4 and not torch.is_autocast_enabled()
+            and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.padding_mode == 'zeros' and (w.shape[0] * w.shape[1]) % 2 == 0):
+        return _OffsetConvStride2.apply(x.contiguous(), w, conv.bias)
+    return conv(x)
+
+
 class Bottleneck(nn.Module):
     expansion = 4
     dcn_takes_groups = False     # (the ResNeXt block hands dcn['groups'] to its deformable conv2, resnext.py:59)
@@ -722,18 +764,22 @@ class Bottleneck(nn.Module):
                 out._kgdet_gate_link = leaving      # (taken -- and removed -- by the next bottleneck of the layer, if there is one)
             return out
         elif self.with_modulated_dcn:
-            offset_mask = self.conv2_offset(out)
+            offset_mask = _offset_conv(self.conv2_offset, out)
             offset = offset_mask[:, :18, :, :]
             mask = offset_mask[:, -9:, :, :].sigmoid()
             out = self.conv2(out, offset, mask)
         else:
-            out = self.conv2(out, self.conv2_offset(out))
+            out = self.conv2(out, _offset_conv(self.conv2_offset, out))
         out = self.relu(self.norm2(out))
-        out = self.norm3(self.conv3(out))
+        # conv3 and the downsample branch on the routes of the dense block (conv_bn; numerics.enumerate_layers lists them for the
+        # envelope guard): as plain modules they ran on MIOpen, whose strided 1x1 forward was seen to change its last bits from
+        # call to call on an MI355X (supposed: float atomics) -- two passes of a block with a deformable conv2 differed
         if self.downsample is not None:
-            identity = self.downsample(x)
-        out += identity
-        return self.relu(out)
+            if isinstance(self.downsample, nn.Sequential) and len(self.downsample) == 2:
+                identity = conv_bn(self.downsample[0], self.downsample[1], x)
+            else:
+                identity = self.downsample(x)
+        return conv_bn(self.conv3, self.norm3, out, relu=True, residual=identity)
 
 
 def make_res_layer(block, inplanes, planes, blocks, stride=1, dilation=1, style='pytorch', with_cp=False,

@@ -158,8 +158,11 @@ def enumerate_layers(model):
         if isinstance(m, backbone.BasicBlock):       # (its forward calls the modules themselves: MIOpen, no envelope)
             seen.update(id(c) for c in m.modules())
         elif isinstance(m, backbone.Bottleneck) and m.with_dcn:
-            pair(prefix + 'conv1', m.conv1, m.norm1)     # (conv2 runs on the DCN kernels, conv3 as a plain module call)
-            seen.update(id(c) for c in m.modules() if c is not m.conv1)
+            # conv1, conv3 and the downsample branch go through backbone.conv_bn as in the dense block; conv2 runs on the DCN
+            # kernels and conv2_offset on torch's fp32 convolution: no envelope for those two
+            pair(prefix + 'conv1', m.conv1, m.norm1)
+            pair(prefix + 'conv3', m.conv3, m.norm3)
+            seen.update(id(c) for c in (m.conv2, getattr(m, 'conv2_offset', None)) if c is not None)
         elif isinstance(m, torch.nn.Sequential):
             if len(m) == 2:                              # a downsample branch: Sequential(conv, BatchNorm)
                 pair(prefix + '0', m[0], m[1])

@@ -18,6 +18,10 @@ Which kernel serves which shape (csrc/dcn_api.hip; HW = H * W of the input map, 
                              HW > 1344: dcn_backward_large.hip per channel run + dcn_bwd_weight_gather<2>
   backward, 'exact'          HW <= 1088 (plan_bwd_lds): dcn_bwd_build_index + dcn_bwd_input_gather (dcn_backward_gather.hip);
                              larger: dcn_backward_large.hip; grad_weight on dcn_bwd_weight_mfma (f32)
+Narrow, numerous weight groups (8 ... 32 groups of 1 ... 32 channels, what a ResNeXt block's dcn['groups'] reaches) take other
+rows of this table -- no plane backward kernel at all (plane_bwd_offset_ok), dcn_bwd_input_gather in BOTH arithmetics up to 1088
+pixels, the zero-padded large-map route from 1089 pixels on, one dcn_bwd_weight_mfma per group beyond 8 channel runs --: the table
+and the tests are in tests/test_gpu_dcn_groups.py.
 """
 import functools
 

@@ -235,3 +235,101 @@ def test_reroute_under_a_captured_step_raises_and_the_runner_recaptures():
     assert torch.isfinite(out['loss']).item()
     assert runner.check_envelope() == []            # still outside, already routed: the step is left alone
     assert runner.graphed.graph is not None
+
+
+# ------------------------------------------------------------------------------------- a bottleneck with a deformable conv2
+def _dcn_block(stride, tiny):
+    """backbone.Bottleneck(64 -> 128, conv2 deformable) with frozen statistics; ``tiny``: channel 7 of norm3 and channel 5 of
+    the downsample BatchNorm have running_var = 1e-12"""
+    torch.manual_seed(11)
+    down = nn.Sequential(nn.Conv2d(64, 128, 1, stride=stride, bias=False), nn.BatchNorm2d(128))
+    blk = backbone.Bottleneck(64, 32, stride=stride, downsample=down,
+                              dcn=dict(modulated=False, deformable_groups=1, fallback_on_stride=False))
+    with torch.no_grad():
+        for m in blk.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+        blk.conv2_offset.weight.normal_(0, 0.05)
+        blk.conv3.weight.normal_(0, 1.0)                 # (|w| up to ~4, as in _pair: x 316 beyond the clamp, x 1.4 far inside)
+        blk.downsample[0].weight.normal_(0, 1.0)
+        if tiny:
+            blk.norm3.running_var[7] = 1e-12
+            blk.downsample[1].running_var[5] = 1e-12
+            # (eight weights of 4 in each of the two rows: |w s| = 1265, beyond the clamp at 511.75 whatever the draw gave)
+            blk.conv3.weight[7, :8, 0, 0] = torch.tensor([4., -4., 4., 4., -4., 4., -4., 4.])
+            blk.downsample[0].weight[5, :8, 0, 0] = torch.tensor([4., 4., -4., 4., -4., -4., 4., 4.])
+    return blk.cuda().eval(), torch.randn(2, 64, 12, 16).cuda()
+
+
+def _dcn_block_reference(blk, x, stride):
+    """the block in float64 on the CPU, conv2 as the grid_sample formulation of tests/torch_ref.py"""
+    import copy
+    from tests import torch_ref
+    ref = copy.deepcopy(blk).double().cpu()
+    with torch.no_grad():
+        xd = x.double().cpu()
+        out = ref.relu(ref.norm1(ref.conv1(xd)))
+        out = torch_ref.deform_conv(out, ref.conv2_offset(out), ref.conv2.weight, stride=stride, padding=1, dilation=1)
+        out = ref.norm3(ref.conv3(ref.relu(ref.norm2(out))))
+        return ref.relu(out + ref.downsample(xd))
+
+
+def _block_errors(y, ref):
+    """_channel_errors with a floor under a channel's scale: a channel the final ReLU leaves (almost) dead is held to 1e-3 of the
+    median channel's scale instead of to its own"""
+    scale = ref.abs().amax((0, 2, 3))
+    d = (y.detach().double().cpu() - ref).abs().amax((0, 2, 3))
+    return (d / scale.clamp_min(1e-3 * float(scale.median()))).numpy()
+
+
+@pytest.mark.parametrize('stride', [1, 2])
+def test_bottleneck_with_deformable_conv2_is_scanned_and_rerouted(stride, monkeypatch):
+    """conv3 and the downsample branch of a bottleneck with a deformable conv2 run through backbone.conv_bn like the dense
+    block's, so the guard lists them (conv2 and conv2_offset, which never take the fp16-part route, stay out): with a tiny
+    variance in norm3 (channel 7) and in the downsample BatchNorm (channel 5) `off` leaves channel 7 of the block's inference
+    output wrong by more than 1e-2 of its own scale, `raise` names the layers, and under `bf16` both weights are rerouted and
+    every channel is within 1e-4 of its own scale of the float64 block (the bar of
+    test_bottleneck_dcn_option_matches_torch_reference, applied per channel) -- in inference and through the training nodes
+    (autograd on, frozen statistics; the strided downsample takes the fp16-part route only there)."""
+    blk, x = _dcn_block(stride, tiny=True)
+    ref = _dcn_block_reference(blk, x, stride)
+    names = [l.name for l in numerics.guard_for(blk).layers]
+    assert names == ['conv1 (folded)', 'conv3 (folded)', 'downsample.0 (folded)', 'conv1', 'conv3', 'downsample.0'], names
+
+    monkeypatch.setenv('KGDET_ENVELOPE', 'off')
+    assert numerics.enforce(blk) == ([], [])
+    with torch.no_grad():
+        e = _block_errors(blk(x), ref)
+    print('dcn block stride %d off: channel 7 %.3e, channel 5 %.3e, others max %.3e' % (stride, e[7], e[5], np.delete(e, [5, 7]).max()))
+    assert e[7] > 1e-2 and np.delete(e, [5, 7]).max() <= 1e-4
+
+    monkeypatch.setenv('KGDET_ENVELOPE', 'raise')
+    with pytest.raises(numerics.EnvelopeError, match=r'conv3 \(folded\)'):
+        numerics.enforce(blk)
+
+    monkeypatch.setenv('KGDET_ENVELOPE', 'bf16')
+    violations = numerics.guard_for(blk).check()
+    assert [v.name for v in violations] == ['conv3 (folded)', 'downsample.0 (folded)']
+    with pytest.warns(RuntimeWarning, match='bf16 parts'):
+        rerouted = numerics.apply_policy(violations)
+    assert len(rerouted) == 2 and conv1x1.bf16_parts(blk.conv3.weight) and conv1x1.bf16_parts(blk.downsample[0].weight)
+    with torch.no_grad():
+        e = _block_errors(blk(x), ref)
+    print('dcn block stride %d bf16 inference: channel 7 %.3e, channel 5 %.3e, max %.3e' % (stride, e[7], e[5], e.max()))
+    assert e.max() <= 1e-4, e
+    xg = x.clone().requires_grad_(True)
+    for _ in range(2):              # (the second scope runs the folded nodes)
+        with conv1x1.step_scope():
+            y = blk(xg)
+        e = _block_errors(y, ref)
+        print('dcn block stride %d bf16 training node: channel 7 %.3e, channel 5 %.3e, max %.3e' % (stride, e[7], e[5], e.max()))
+        assert e.max() <= 1e-4, e
+
+
+def test_bottleneck_with_deformable_conv2_inside_the_envelope_is_left_alone():
+    blk, x = _dcn_block(2, tiny=False)
+    assert numerics.guard_for(blk).check() == [] and numerics.enforce(blk) == ([], [])
+    assert not conv1x1._bf16_parts
+    with torch.no_grad():
+        assert _block_errors(blk(x), _dcn_block_reference(blk, x, 2)).max() <= 1e-4
