@@ -1173,6 +1173,50 @@ int kgdet_jpeg_decode(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_de
 int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n,
                              void *workspace, size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status,
                              void *stream, int32_t stages);
+/* The files cameras and phones write (jpeg.parse_header(camera=True), jpeg.decode_restatement(camera=True)): the same
+ * arguments, the same job table and the same layout of `src`, and additionally
+ *   mode KGDET_JPEG_DECODE_422   Y / Cb / Cr sampled 2x1 / 1x1 / 1x1: an MCU is 16 wide and 8 high, its blocks Y left, Y right,
+ *                                Cb, Cr; chroma by libjpeg's h2v1 fancy upsampling over ceil(W / 2) samples a row,
+ *                                out[2x] = (3 c[x] + c[x-1] + 1) >> 2, out[2x+1] = (3 c[x] + c[x+1] + 2) >> 2, neighbours
+ *                                replicated at the edges (a row of two samples is replicated, as libjpeg does);
+ *   reserved                     the restart interval in MCUs, 0 .. 65535, 0: none.
+ * For the files kgdet_jpeg_decode takes the pictures are the same bits.  With an interval of R MCUs the scan holds
+ * nint = ceil(MCUs / R) intervals between the markers RSTm, m = 0, 1, .. 7, 0, ..; every interval is decoded on its own from the
+ * state (its first bit, slot 0, a DC code next) with predictors 0, holds exactly its share of blocks (R MCUs, the last one the
+ * remainder) and ends within the last byte of its data.  status may also become KGDET_JPEG_DECODE_BAD_RESTART: a marker out of
+ * turn, a missing or a surplus marker, an interval with another block count than its share or another end -- an interval cut
+ * short at its tail included: the true parse stops in front of the symbol that no longer fits.  _BAD_SCAN stays what an invalid
+ * code on the true parse gives, and what a wrong count or end gives in a job with interval 0.  A restart marker in a job with
+ * interval 0 ends the scan: _NOT_EOI.  0xFF 0xFF ends the scan too (no fill bytes in front of a marker).
+ * Kernels (all on `stream`, no read-back, no global atomics):
+ *   unstuff  a workgroup per image, as above; a restart marker does not end the scan and both its bytes are dropped.  The
+ *            lane that meets one learns its ordinal from the same workgroup scan that places the kept bytes, checks its number
+ *            and the count, and writes where the next interval's un-stuffed bytes begin.  The INTERVAL TABLE of an image in the
+ *            workspace: uint32 [nint + 1] begin, uint32 [nint + 1] length (bytes), uint32 [nint + 1] first subsequence -- an
+ *            interval is cut into subsequences of KGDET_JPEG_DECODE_SUBSEQ_BITS bits from ITS first bit, at least one.
+ *   huffman  a workgroup per (tile, image).  A tile is a run of whole intervals: as many as hold
+ *            KGDET_JPEG_DECODE_CHUNK_LANES subsequences' worth of the scan's bytes on average, 1 .. CHUNK_LANES of them (the host's
+ *            plan, from scan_bytes and the frame alone), so an image with more than a chunk of stream is decoded by several
+ *            workgroups.  A lane per subsequence, CHUNK_LANES at a time; a lane that holds an interval's first subsequence enters
+ *            with the true state and never takes its predecessor's exit; where a chunk begins inside an interval it follows the
+ *            chunk before it as above.  A uniform picture with interval 1 has one-byte intervals: a lane each.  Block indices
+ *            are i * R * blocks-per-MCU plus a segmented scan; stores stay inside the interval's own blocks.  The DC scan
+ *            restarts at every interval.  Each tile leaves uint32 (status, rounds) in the workspace.
+ *   verdict  a workgroup per image: the status of the first tile that refused, and into the `rounds` words of the workspace
+ *            header the most rounds of any chunk of any tile.
+ *   idct, colour  as above, with mode 3's slots and the h2v1 rule.
+ * Refused with KGDET_E_SHAPE before any launch: everything kgdet_jpeg_decode refuses (mode above 3 here), reserved outside
+ * [0, 65535], a workspace smaller than kgdet_jpeg_decode_camera_workspace_bytes(jobs, n), which accounts for the interval tables
+ * and the tiles' words.  kgdet_jpeg_decode itself keeps refusing mode 3 and never reads `reserved`. */
+#define KGDET_JPEG_DECODE_422 3
+#define KGDET_JPEG_DECODE_BAD_RESTART 4
+size_t kgdet_jpeg_decode_camera_workspace_bytes(const kgdet_jpeg_decode_job *jobs, int32_t n);
+int kgdet_jpeg_decode_camera(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
+                             size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream);
+/* For timing only: kgdet_jpeg_decode_camera cut short after `stages` of unstuff, huffman + verdict, idct, colour. */
+int kgdet_jpeg_decode_camera_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n,
+                                    void *workspace, size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status,
+                                    void *stream, int32_t stages);
 int kgdet_nms(const float *dets, int64_t n, float iou_thr, int64_t *keep, int64_t *num_keep,
               void *workspace, size_t workspace_bytes, void *stream);
 int kgdet_nms_batched(const float *dets, const int64_t *seg_offsets, int32_t num_segments,

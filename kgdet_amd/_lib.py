@@ -160,6 +160,13 @@ def lib():
             L.kgdet_jpeg_decode.argtypes = [vp, i64, vp, i32, vp, ctypes.c_size_t, vp, i64, vp, vp]
             L.kgdet_jpeg_decode_stages.restype = ctypes.c_int
             L.kgdet_jpeg_decode_stages.argtypes = L.kgdet_jpeg_decode.argtypes + [i32]
+        if hasattr(L, 'kgdet_jpeg_decode_camera'):   # the same signatures: 4:2:2 files and restart intervals
+            L.kgdet_jpeg_decode_camera_workspace_bytes.restype = ctypes.c_size_t
+            L.kgdet_jpeg_decode_camera_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+            L.kgdet_jpeg_decode_camera.restype = ctypes.c_int
+            L.kgdet_jpeg_decode_camera.argtypes = L.kgdet_jpeg_decode.argtypes
+            L.kgdet_jpeg_decode_camera_stages.restype = ctypes.c_int
+            L.kgdet_jpeg_decode_camera_stages.argtypes = L.kgdet_jpeg_decode_stages.argtypes
         _lib = L
     return _lib
 

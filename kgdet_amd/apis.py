@@ -50,7 +50,7 @@ def train_detector(model, dataset, cfg, validate=False, logger=None):
     device = next(model.parameters()).device
     opts = dict(_get(cfg, 'loader', {}))
     device_preprocess = bool(opts.get('device_preprocess', False))
-    device_decode = bool(opts.get('device_decode', False))
+    device_decode = opts.get('device_decode', False)           # False, True or 'camera' (jpeg.decode_switch)
     loader = build_dataloader(dataset, cfg.data.imgs_per_gpu, cfg.data.workers_per_gpu, _get(cfg, 'gpus', 1), dist=False,
                               device=device, device_preprocess=device_preprocess, prefetch=opts.get('prefetch', 2),
                               device_decode=device_decode)

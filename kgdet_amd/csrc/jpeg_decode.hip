@@ -47,6 +47,8 @@ constexpr int kTableBytes = KGDET_JPEG_DECODE_TABLE_BYTES;
 constexpr long long kMaxScanBytes = 1ll << 28;      // 8 * bytes fits 32 bits
 constexpr int kStreamPad = 32;
 constexpr int kBackThreads = 256;
+// camera entry points: the stream a tile of whole restart intervals holds on average, a chunk's worth
+constexpr long long kTileBytes = (long long)kLanes * kSub / 8;
 
 typedef unsigned char u8;
 typedef unsigned int u32;
@@ -76,8 +78,16 @@ struct Geometry {
   int pw0, ph0, pw1, ph1;                           // the luma plane's and a chroma plane's padded extent
 };
 
+// CAM: the camera entry points' instance, which also knows mode 3 (an MCU 16 wide and 8 high, 4 blocks)
+template <bool CAM = false>
 __host__ __device__ inline Geometry geometry(int H, int W, int mode) {
   Geometry g;
+  if (CAM && mode == KGDET_JPEG_DECODE_422) {
+    g.mw = (W + 15) / 16, g.mh = (H + 7) / 8, g.bpm = 4;
+    g.nblocks = g.mw * g.mh * g.bpm;
+    g.pw0 = g.mw * 16, g.ph0 = g.mh * 8, g.pw1 = g.mw * 8, g.ph1 = g.mh * 8;
+    return g;
+  }
   const int unit = mode == KGDET_JPEG_DECODE_420 ? 16 : 8;
   g.mw = (W + unit - 1) / unit, g.mh = (H + unit - 1) / unit;
   g.bpm = mode == KGDET_JPEG_DECODE_420 ? 6 : (mode == KGDET_JPEG_DECODE_444 ? 3 : 1);
@@ -198,7 +208,7 @@ __device__ __forceinline__ u32 peek(const u32 *__restrict__ words, u32 p) {
 
 // jpeg.decode_span: the symbols that start in [st.p, limit) of a stream of `total` bits; `done` = blocks completed.  WRITE: the
 // non-zero values go to block `blk` + done of `coef` when that is a block of the frame, else `beyond` is set.
-template <bool WRITE>
+template <bool WRITE, bool CAM = false>
 __device__ __forceinline__ State decode_span(State st, u32 start, u32 limit, u32 total, const u32 *__restrict__ words,
                                              const Huff *s_h, const u8 *s_tab, const u8 *s_zz, int mode, int bpm, int &done,
                                              short *__restrict__ coef, int blk, int nblocks, bool &beyond) {
@@ -208,7 +218,7 @@ __device__ __forceinline__ State decode_span(State st, u32 start, u32 limit, u32
   int b = (int)(st.bz >> 8), z = (int)(st.bz & 255u);
   const State invalid = {kInvalid, kInvalid};
   while (p < limit && p < total) {
-    const int comp = mode == KGDET_JPEG_DECODE_420 ? max(b - 3, 0) : b;
+    const int comp = mode == KGDET_JPEG_DECODE_420 ? max(b - 3, 0) : (CAM && mode == KGDET_JPEG_DECODE_422 ? max(b - 1, 0) : b);
     const Huff &T = s_h[z == 0 ? (s_tab[comp] & 1) : 2 + (s_tab[3 + comp] & 1)];
     const u32 w32 = peek(words, p);
     const u32 w16 = w32 >> 16;
@@ -278,6 +288,42 @@ __device__ __forceinline__ State decode_span(State st, u32 start, u32 limit, u32
   State out;
   out.p = p, out.bz = (u32)b << 8 | (u32)z;
   return out;
+}
+
+// the look-ups of an image's four Huffman tables, Annex C / F.2.2.3, by the whole workgroup; every index made from the table
+// block is clamped.  Ends behind a barrier.  (jpeg_huffman_kernel keeps the same statements in its body: called from there the
+// compiler allocates that kernel's registers differently, and the old entry point's code stays instruction for instruction what
+// it was.)
+__device__ __forceinline__ void build_tables(const u8 *__restrict__ tab, Huff *s_h, u8 *s_tab, u8 *s_zz, int *s_bad) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < 4 * 256; i += kLanes) s_h[i >> 8].lut[i & 255] = 0;
+  if (tid < 64) s_zz[tid] = d_zigzag[tid];
+  if (tid < 6) s_tab[tid] = tab[800 + tid];
+  if (tid == 0) *s_bad = 0;
+  __syncthreads();
+  if (tid < 4) {
+    const int ac = tid >> 1, th = tid & 1, nvals = ac ? 256 : 16;
+    const u8 *bits = tab + (ac ? 256 : 192) + 16 * th, *vals = tab + (ac ? 288 + 256 * th : 224 + 16 * th);
+    Huff &T = s_h[tid];
+    int code = 0, k = 0;
+    T.maxcode[0] = -1, T.valoff[0] = 0;
+    for (int len = 1; len <= 16; ++len) {
+      const int count = bits[len - 1];
+      T.valoff[len] = k - code;
+      for (int i = 0; i < count; ++i, ++code, ++k) {
+        if (len <= 8) {
+          const int lo = code << (8 - len);
+          const unsigned short entry = (unsigned short)(len << 8 | vals[min(k, nvals - 1)]);
+          for (int j = 0; j < (1 << (8 - len)); ++j)
+            if (lo + j < 256) T.lut[lo + j] = entry;
+        }
+      }
+      T.maxcode[len] = count ? code - 1 : -1;
+      code <<= 1;
+    }
+    for (int i = 0; i < 256; ++i) T.vals[i] = i < nvals ? vals[i] : 0;
+  }
+  __syncthreads();
 }
 
 __global__ __launch_bounds__(kLanes) void jpeg_huffman_kernel(const DecArgs args, const u8 *__restrict__ src, u8 *__restrict__ ws,
@@ -417,6 +463,319 @@ __global__ __launch_bounds__(kLanes) void jpeg_huffman_kernel(const DecArgs args
   }
 }
 
+// ---- 1c / 2c. the camera entry points: restart intervals -------------------------------------------------------------------
+// kgdet_jpeg_decode_camera (jpeg.decode_restatement(camera=True)): 4:2:2 files (mode 3) and restart intervals.  With an
+// interval of R MCUs the scan holds nint = ceil(MCUs / R) pieces between RSTm markers; at every piece's first bit the true
+// state is known ((0, 0), predictors 0) and so is the index of its first block, i * R * blocks per MCU.
+//  1c. unstuff  as above, and: a restart marker does not end the scan, both its bytes are dropped, and the lane that holds its
+//      0xFF writes where the next interval's un-stuffed bytes begin into the image's interval table (its ordinal is the
+//      scan of the marker counts, which rides in the high half of the kept counts' scan).  The ordinal fixes the marker's number
+//      and must stay below nint - 1; at the end there must be nint - 1 of them: else KGDET_JPEG_DECODE_BAD_RESTART.  Then per
+//      interval its length and the exclusive scan of its subsequences, max(1, ceil(bits / kSub)), counted from ITS first bit.
+//  2c. huffman  a workgroup per (tile, image); a tile is a run of `per_tile` whole intervals (the host's plan: about a chunk's
+//      worth of stream, at most kLanes intervals).  A lane per subsequence of an interval, kLanes at a time; a lane that holds
+//      an interval's first subsequence enters with the true state and never takes its predecessor's exit, the others iterate as
+//      above, within the interval's own bits.  The block index of a lane is the interval's first block plus the SEGMENTED scan
+//      of the completed-block counts (prefix minus the prefix at the interval's first lane, or the blocks carried over from
+//      earlier chunks); stores are confined to the interval's own blocks.  The lane of an interval's last subsequence checks its
+//      share of blocks and its end.  Then the DC scan of the tile's MCUs, restarting at every interval.  A tile leaves
+//      (status, rounds) in the workspace; `verdict` (a workgroup per image) takes the first tile's non-zero status and the most
+//      rounds: no atomics on global memory, and the status does not depend on which tile ran first.
+struct CamImage {
+  i64 table_off, tile_off;                          // inside the workspace: uint32 begin / length / first subsequence [nint + 1] each; uint32 [ntiles][2]
+  int interval, nint, per_tile, ntiles;             // R (0: none), intervals, intervals per tile, tiles
+};
+
+struct CamArgs {
+  CamImage img[kMaxImages];
+};
+
+__device__ __forceinline__ int slot_component(int mode, int k) {
+  return mode == KGDET_JPEG_DECODE_420 ? (k < 4 ? 0 : k - 3) : (mode == KGDET_JPEG_DECODE_422 ? (k < 2 ? 0 : k - 1) : (k < 3 ? k : 0));
+}
+
+__global__ __launch_bounds__(kLanes) void jpeg_unstuff_camera_kernel(const DecArgs args, const CamArgs cam,
+                                                                     const u8 *__restrict__ src, u8 *__restrict__ ws,
+                                                                     u32 *__restrict__ lens, int *__restrict__ status) {
+  __shared__ u32 s_end;
+  __shared__ int s_w[kWaves];
+  __shared__ int s_bad;
+  const int tid = threadIdx.x, im = blockIdx.x;
+  const DecImage &I = args.img[im];
+  const CamImage &C = cam.img[im];
+  const u8 *__restrict__ in = src + I.scan_off;
+  u8 *__restrict__ out = ws + I.stream_off;
+  u32 *begin = (u32 *)(ws + C.table_off), *length = begin + (C.nint + 1), *first = length + (C.nint + 1);
+  const u32 nbytes = (u32)I.scan_bytes;
+  const bool rst = C.interval > 0;
+  if (tid == 0) s_end = 0xffffffffu, s_bad = 0;
+  __syncthreads();
+  for (u32 k = tid; k + 1 < nbytes; k += kLanes) {
+    if (in[k] == 0xFF) {
+      const u8 nx = in[k + 1];
+      if (nx != 0 && !(rst && nx >= 0xD0 && nx <= 0xD7)) {
+        atomicMin(&s_end, k);
+        break;
+      }
+    }
+  }
+  __syncthreads();
+  const u32 end = s_end;
+  if (end == 0xffffffffu || in[end + 1] != 0xD9) {  // (uniform)
+    if (tid == 0) {
+      status[im] = end == 0xffffffffu ? KGDET_JPEG_DECODE_NO_MARKER : KGDET_JPEG_DECODE_NOT_EOI;
+      lens[im] = 0;
+    }
+    return;
+  }
+  // before `end` every 0xFF is followed by 0x00 or, with an interval, by RSTm: never by another 0xFF
+  u32 carry = 0, markers = 0;
+  for (u32 base = 0; base < end; base += 16 * kLanes) {
+    const u32 k0 = base + 16 * tid;
+    u8 b[17];
+    u32 keep = 0, lead = 0;
+    int count = 0, nlead = 0;
+    if (k0 < end) {
+      u8 prev = k0 ? in[k0 - 1] : 0;
+#pragma unroll
+      for (int j = 0; j < 17; ++j) b[j] = k0 + j <= end ? in[k0 + j] : 0;       // (in[end] is the 0xFF of EOI)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const bool live = k0 + j < end;
+        const bool leads = rst && live && b[j] == 0xFF && b[j + 1] >= 0xD0 && b[j + 1] <= 0xD7;
+        const bool follows = prev == 0xFF && (b[j] == 0 || (rst && b[j] >= 0xD0 && b[j] <= 0xD7));
+        const bool kept = live && !leads && !follows;
+        keep |= kept ? 1u << j : 0u;
+        lead |= leads ? 1u << j : 0u;
+        count += kept ? 1 : 0;
+        nlead += leads ? 1 : 0;
+        prev = b[j];
+      }
+    }
+    int total;
+    const int at = block_exclusive(count | nlead << 16, s_w, total);            // kept bytes <= 16384 a pass: the halves do not mix
+    u8 *o = out + carry + (u32)(at & 0xffff);
+    u32 ordinal = markers + (u32)(at >> 16);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if (lead >> j & 1u) {
+        if (ordinal + 1 < (u32)C.nint) {
+          begin[ordinal + 1] = (u32)(o - out);
+          if ((u32)(b[j + 1] - 0xD0) != (ordinal & 7u)) s_bad = 1;              // (an idempotent flag store)
+        } else {
+          s_bad = 1;                                                            // a surplus marker
+        }
+        ++ordinal;
+      }
+      if (keep >> j & 1u) *o++ = b[j];
+    }
+    carry += (u32)(total & 0xffff);
+    markers += (u32)(total >> 16);
+  }
+  if (tid < kStreamPad) out[carry + tid] = 0xFF;
+  if (tid == 0) {
+    begin[0] = 0, begin[C.nint] = carry;
+    if (markers != (u32)(C.nint - 1)) s_bad = 1;
+  }
+  __syncthreads();
+  if (s_bad) {                                      // (uniform)
+    if (tid == 0) {
+      status[im] = KGDET_JPEG_DECODE_BAD_RESTART;
+      lens[im] = 0;
+    }
+    return;
+  }
+  u32 subs = 0;
+  for (int i0 = 0; i0 <= C.nint; i0 += kLanes) {
+    const int i = i0 + tid;
+    u32 bytes = 0;
+    if (i < C.nint) bytes = begin[i + 1] - begin[i];
+    int total;
+    const int at = block_exclusive(i < C.nint ? (int)max((bytes + kSub / 8 - 1) / (kSub / 8), 1u) : 0, s_w, total);
+    if (i <= C.nint) length[i] = bytes, first[i] = subs + (u32)at;
+    subs += (u32)total;
+  }
+  if (tid == 0) {
+    status[im] = 0;
+    lens[im] = carry;
+  }
+}
+
+__global__ __launch_bounds__(kLanes) void jpeg_huffman_camera_kernel(const DecArgs args, const CamArgs cam,
+                                                                     const u8 *__restrict__ src, u8 *__restrict__ ws,
+                                                                     const int *__restrict__ status) {
+  __shared__ Huff s_h[4];                           // DC 0, DC 1, AC 0, AC 1
+  __shared__ u8 s_tab[8], s_zz[64];
+  __shared__ u32 s_exit_p[kLanes], s_exit_bz[kLanes];
+  __shared__ u32 s_first[kLanes + 1];               // the first subsequence of the tile's intervals, and the end
+  __shared__ int s_pre[kLanes];                     // the chunk's exclusive scan of the block counts
+  __shared__ int s_dc[3][kLanes];
+  __shared__ int s_w[kWaves];
+  __shared__ int s_bad, s_count, s_carry;
+  const int tid = threadIdx.x, im = blockIdx.y, tile = blockIdx.x;
+  if (status[im] != 0) return;                      // (uniform: the first kernel refused the scan)
+  const CamImage &C = cam.img[im];
+  if (tile >= C.ntiles) return;                     // (uniform)
+  const DecImage &I = args.img[im];
+  const Geometry g = geometry<true>(I.H, I.W, I.mode);
+  const u8 *__restrict__ tab = src + I.tab_off;
+  const u32 *__restrict__ words = (const u32 *)(ws + I.stream_off);
+  short *__restrict__ coef = (short *)(ws + I.coef_off);
+  const u32 *__restrict__ begin = (const u32 *)(ws + C.table_off), *__restrict__ length = begin + (C.nint + 1),
+                         *__restrict__ first = length + (C.nint + 1);
+  u32 *__restrict__ verdict = (u32 *)(ws + C.tile_off) + 2 * tile;
+  const int nm = g.mw * g.mh, R = C.interval ? min(C.interval, nm) : nm;        // MCUs of an interval
+  const int i0 = tile * C.per_tile, i1 = min(i0 + C.per_tile, C.nint), ni = i1 - i0;      // ni <= kLanes
+  build_tables(tab, s_h, s_tab, s_zz, &s_bad);
+  if (tid == 0) s_count = 0, s_carry = 0;
+  for (int k = tid; k <= ni; k += kLanes) s_first[k] = first[i0 + k];
+  __syncthreads();
+  const u32 sub0 = s_first[0], sub1 = s_first[ni];
+  State chunk_entry = {kInvalid, kInvalid};         // (the tile's first lane holds an interval start)
+  int carried = 0;                                  // blocks the interval that runs into this chunk completed in earlier ones
+  bool bad_scan = false, bad_count = false;
+  int most_rounds = 0;
+  for (u32 base = sub0; base < sub1; base += kLanes) {
+    const int nl = (int)min((u32)kLanes, sub1 - base);
+    const bool live = tid < nl;
+    u32 j = 0, start = 0, limit = 0, total = 0;
+    int share = 0, blk0 = 0;
+    bool tail = false;
+    if (live) {
+      const u32 l = base + (u32)tid;
+      int lo = 0, hi = ni - 1;                      // the interval: the last one that begins at or before subsequence l
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_first[mid] <= l)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      const int itv = i0 + lo;
+      j = l - s_first[lo], tail = l + 1 == s_first[lo + 1];
+      const u32 at = begin[itv];
+      start = 8u * at + j * kSub, limit = start + kSub, total = 8u * (at + length[itv]);
+      share = min(R, nm - itv * R) * g.bpm, blk0 = itv * R * g.bpm;
+    }
+    const bool head = j == 0;
+    State entry = {start, 0u}, ex = entry;
+    if (tid == 0 && !head) entry = chunk_entry;
+    bool need = live;
+    int done = 0;
+    bool settled = false, beyond = false;
+    for (int round = 0; round <= nl; ++round) {
+      if (need) {
+        ex = decode_span<false, true>(entry, start, limit, total, words, s_h, s_tab, s_zz, I.mode, g.bpm, done, coef, 0, 0, beyond);
+        s_exit_p[tid] = ex.p, s_exit_bz[tid] = ex.bz;
+      }
+      __syncthreads();
+      need = false;
+      if (tid > 0 && live && !head) {
+        State in;
+        in.p = s_exit_p[tid - 1], in.bz = s_exit_bz[tid - 1];
+        if (in.p == kInvalid) in.p = start, in.bz = 0u;               // an invalid parse tells nothing: the cold start again
+        need = !same(in, entry);
+        entry = in;
+      }
+      if (!__syncthreads_or(need ? 1 : 0)) {
+        settled = true;
+        most_rounds = max(most_rounds, round + 1);
+        break;
+      }
+    }
+    if (!settled) bad_scan = true;                  // (cannot happen: round k fixes lane k)
+    int all;
+    const int pre = block_exclusive(live ? done : 0, s_w, all);
+    s_pre[tid] = pre;
+    __syncthreads();
+    if (live) {
+      const int before = j <= (u32)tid ? pre - s_pre[tid - (int)j] : carried + pre;       // blocks of the interval before the lane
+      int again;
+      const State wx = decode_span<true, true>(entry, start, limit, total, words, s_h, s_tab, s_zz, I.mode, g.bpm, again, coef,
+                                               blk0 + before, blk0 + share, beyond);
+      if (wx.p == kInvalid) bad_scan = true;                           // the TRUE parse met an invalid code
+      if (!same(wx, ex) || again != done) bad_scan = true;             // (cannot happen: the fixpoint is the true parse)
+      if (beyond) bad_count = true;                                    // more blocks than the interval's share
+      if (tail && !(ex.p != kInvalid && (ex.bz & 255u) == 0 && before + done == share && ex.p <= total && total - ex.p < 8))
+        bad_count = true;
+      if (tid == nl - 1) s_carry = before + done;
+    }
+    chunk_entry.p = s_exit_p[nl - 1], chunk_entry.bz = s_exit_bz[nl - 1];
+    __syncthreads();                                // (the exits and the scan are read before the next chunk overwrites them)
+    carried = s_carry;
+  }
+  if (bad_scan) s_bad = 1;                          // (idempotent flag stores)
+  if (bad_count) s_count = 1;
+  __syncthreads();
+  const int code = s_bad ? KGDET_JPEG_DECODE_BAD_SCAN
+                         : (s_count ? (C.interval ? KGDET_JPEG_DECODE_BAD_RESTART : KGDET_JPEG_DECODE_BAD_SCAN) : 0);
+  if (tid == 0) verdict[0] = (u32)code, verdict[1] = (u32)most_rounds;
+  if (code) return;                                 // (uniform)
+  // DC values of the tile's MCUs: the inclusive scan of the differences per component restarts at every interval
+  const int mfirst = i0 * R, mend = min(i1 * R, nm);
+  int carry[3] = {0, 0, 0};                         // the sums of the segment that runs into this chunk
+  for (int m0 = mfirst; m0 < mend; m0 += kLanes) {
+    const int m = m0 + tid;
+    int d[6] = {0, 0, 0, 0, 0, 0}, sum[3] = {0, 0, 0};
+    if (m < mend) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k)
+        if (k < g.bpm) d[k] = coef[((size_t)m * g.bpm + k) * 64];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) sum[slot_component(I.mode, k)] += d[k];
+    int pre[3], all[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      pre[c] = block_exclusive(sum[c], s_w, all[c]);
+      s_dc[c][tid] = pre[c];
+    }
+    __syncthreads();
+    if (m < mend) {
+      const int seg = mfirst + (m - mfirst) / R * R;                   // the first MCU of m's interval
+      int before[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) before[c] = seg >= m0 ? pre[c] - s_dc[c][seg - m0] : carry[c] + pre[c];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        if (k < g.bpm) {
+          const int c = slot_component(I.mode, k);
+          before[c] += d[k];
+          coef[((size_t)m * g.bpm + k) * 64] = (short)min(max(before[c], -32768), 32767);
+        }
+      }
+    }
+    const int m1 = m0 + kLanes;
+    if (m1 < mend) {                                // (uniform)
+      const int seg = mfirst + (m1 - mfirst) / R * R;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) carry[c] = seg >= m1 ? 0 : (seg >= m0 ? all[c] - s_dc[c][seg - m0] : carry[c] + all[c]);
+    }
+    __syncthreads();                                // (the scans are read before the next chunk overwrites them)
+  }
+}
+
+// an image's status and rounds from its tiles': the first tile that refused, the most rounds
+__global__ __launch_bounds__(kBackThreads) void jpeg_verdict_camera_kernel(const CamArgs cam, const u8 *__restrict__ ws,
+                                                                           u32 *__restrict__ rounds, int *__restrict__ status) {
+  __shared__ u32 s_tile, s_rounds;
+  const int tid = threadIdx.x, im = blockIdx.x;
+  if (status[im] != 0) return;                      // (uniform)
+  const CamImage &C = cam.img[im];
+  const u32 *__restrict__ verdict = (const u32 *)(ws + C.tile_off);
+  if (tid == 0) s_tile = 0xffffffffu, s_rounds = 0;
+  __syncthreads();
+  for (int t = tid; t < C.ntiles; t += kBackThreads) {
+    if (verdict[2 * t]) atomicMin(&s_tile, (u32)t);
+    atomicMax(&s_rounds, verdict[2 * t + 1]);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    rounds[im] = s_rounds;
+    if (s_tile != 0xffffffffu) status[im] = (int)verdict[2 * s_tile];
+  }
+}
+
 // ---- 3. idct ----------------------------------------------------------------------------------------------------------------
 // jidctint.c's butterfly on eight values; out[k] before the descale
 __device__ __forceinline__ void idct_1d(const i64 *in, i64 *out) {
@@ -438,13 +797,15 @@ __device__ __forceinline__ void idct_1d(const i64 *in, i64 *out) {
   out[3] = t13 + o0, out[4] = t13 - o0;
 }
 
+// CAM: the camera entry points' instance, which also maps mode 3's slots (Y left, Y right, Cb, Cr)
+template <bool CAM>
 __global__ __launch_bounds__(kBackThreads) void jpeg_idct_kernel(const DecArgs args, const u8 *__restrict__ src,
                                                                  u8 *__restrict__ ws, const int *__restrict__ status) {
   __shared__ u8 s_q[3][64];
   const int tid = threadIdx.x, im = blockIdx.y;
   if (status[im] != 0) return;                      // (uniform)
   const DecImage &I = args.img[im];
-  const Geometry g = geometry(I.H, I.W, I.mode);
+  const Geometry g = geometry<CAM>(I.H, I.W, I.mode);
   if (tid < 192) s_q[tid >> 6][tid & 63] = src[I.tab_off + tid];
   __syncthreads();
   const short *__restrict__ coef = (const short *)(ws + I.coef_off);
@@ -456,6 +817,8 @@ __global__ __launch_bounds__(kBackThreads) void jpeg_idct_kernel(const DecArgs a
     int comp, by, bx, pw;
     if (I.mode == KGDET_JPEG_DECODE_420 && slot < 4) {
       comp = 0, by = 2 * my + (slot >> 1), bx = 2 * mx + (slot & 1), pw = g.pw0;
+    } else if (CAM && I.mode == KGDET_JPEG_DECODE_422) {
+      comp = slot < 2 ? 0 : slot - 1, by = my, bx = slot < 2 ? 2 * mx + slot : mx, pw = slot < 2 ? g.pw0 : g.pw1;
     } else {
       comp = I.mode == KGDET_JPEG_DECODE_420 ? slot - 3 : slot;
       by = my, bx = mx, pw = comp ? g.pw1 : g.pw0;
@@ -510,14 +873,23 @@ __device__ __forceinline__ int fancy(const u8 *__restrict__ c, int pw, int ch, i
   return (3 * v + vn + ((x & 1) ? 7 : 8)) >> 4;
 }
 
+// libjpeg's h2v1 fancy upsampling of a chroma row of cw real samples; a row of up to two samples is replicated
+__device__ __forceinline__ int fancy_h2v1(const u8 *__restrict__ row, int cw, int x) {
+  const int cx = x >> 1;
+  if (cw <= 2) return row[cx];
+  const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0);
+  return (3 * row[cx] + row[nx] + ((x & 1) ? 2 : 1)) >> 2;
+}
+
 __device__ __forceinline__ u32 clamp255(int v) { return (u32)min(max(v, 0), 255); }
 
+template <bool CAM>
 __global__ __launch_bounds__(kBackThreads) void jpeg_colour_kernel(const DecArgs args, const u8 *__restrict__ ws,
                                                                    u8 *__restrict__ out, const int *__restrict__ status) {
   const int tid = threadIdx.x, im = blockIdx.y;
   if (status[im] != 0) return;                      // (uniform)
   const DecImage &I = args.img[im];
-  const Geometry g = geometry(I.H, I.W, I.mode);
+  const Geometry g = geometry<CAM>(I.H, I.W, I.mode);
   const u8 *__restrict__ py = ws + I.plane_off;
   const u8 *__restrict__ pcb = py + (size_t)g.pw0 * g.ph0, *__restrict__ pcr = pcb + (size_t)g.pw1 * g.ph1;
   u8 *__restrict__ dst = out + I.dst_off;
@@ -543,6 +915,8 @@ __global__ __launch_bounds__(kBackThreads) void jpeg_colour_kernel(const DecArgs
           int cb, cr;
           if (I.mode == KGDET_JPEG_DECODE_420) {
             cb = fancy(pcb, g.pw1, ch, cw, y, x) - 128, cr = fancy(pcr, g.pw1, ch, cw, y, x) - 128;
+          } else if (CAM && I.mode == KGDET_JPEG_DECODE_422) {
+            cb = fancy_h2v1(pcb + (size_t)y * g.pw1, cw, x) - 128, cr = fancy_h2v1(pcr + (size_t)y * g.pw1, cw, x) - 128;
           } else {
             cb = pcb[(size_t)y * g.pw1 + x] - 128, cr = pcr[(size_t)y * g.pw1 + x] - 128;
           }
@@ -576,19 +950,28 @@ bool disjoint(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) 
 
 struct Layout {
   size_t lens, coef, coef_bytes, total;
+  int most_tiles;                                   // camera: of any image
 };
 
 // the jobs' sizes -> kernel arguments and the workspace's layout: the stream lengths, the streams, the coefficients of all
-// images (one run, zeroed by one memset), the planes.  src_bytes / out_bytes < 0: offsets are not checked
-int plan(const char *what, const kgdet_jpeg_decode_job *jobs, int n, int64_t src_bytes, int64_t out_bytes, DecArgs &args, Layout &L) {
+// images (one run, zeroed by one memset), the planes.  src_bytes / out_bytes < 0: offsets are not checked.  `cam` (the camera
+// entry points): mode 3 is taken, `reserved` is the restart interval, and behind the planes follow per image the interval table
+// (three uint32 [intervals + 1]) and the tiles' verdicts (two uint32 a tile).  The tile plan: as many whole intervals as hold
+// a chunk's worth of the scan's bytes on average, 1 .. kLanes of them.
+int plan(const char *what, const kgdet_jpeg_decode_job *jobs, int n, int64_t src_bytes, int64_t out_bytes, DecArgs &args, Layout &L,
+         CamArgs *cam = nullptr) {
   args = {};
   args.n = n;
+  L.most_tiles = 1;
   for (int i = 0; i < n; ++i) {
     const kgdet_jpeg_decode_job &J = jobs[i];
     KGDET_CHECK_SHAPE(J.H >= 1 && J.H <= kMaxSide && J.W >= 1 && J.W <= kMaxSide, "%s: image %d: %d x %d (sides 1 .. %d)", what, i,
                       J.H, J.W, kMaxSide);
-    KGDET_CHECK_SHAPE(J.mode == KGDET_JPEG_DECODE_GREY || J.mode == KGDET_JPEG_DECODE_444 || J.mode == KGDET_JPEG_DECODE_420,
+    KGDET_CHECK_SHAPE(J.mode == KGDET_JPEG_DECODE_GREY || J.mode == KGDET_JPEG_DECODE_444 || J.mode == KGDET_JPEG_DECODE_420 ||
+                          (cam && J.mode == KGDET_JPEG_DECODE_422),
                       "%s: image %d: mode %d", what, i, J.mode);
+    KGDET_CHECK_SHAPE(!cam || (J.reserved >= 0 && J.reserved <= 65535), "%s: image %d: a restart interval of %d MCUs (0 .. 65535)",
+                      what, i, J.reserved);
     KGDET_CHECK_SHAPE(J.scan_bytes >= 2 && J.scan_bytes <= kMaxScanBytes, "%s: image %d: a scan of %lld bytes (2 .. 2^28)", what, i,
                       (long long)J.scan_bytes);
     const int64_t pixels = 3ll * J.H * J.W;
@@ -622,13 +1005,31 @@ int plan(const char *what, const kgdet_jpeg_decode_job *jobs, int n, int64_t src
   L.coef = at;
   for (int i = 0; i < n; ++i) {
     args.img[i].coef_off = (i64)at;
-    at += (size_t)geometry(args.img[i].H, args.img[i].W, args.img[i].mode).nblocks * 128;
+    at += (size_t)geometry<true>(args.img[i].H, args.img[i].W, args.img[i].mode).nblocks * 128;
   }
   L.coef_bytes = at - L.coef;
   for (int i = 0; i < n; ++i) {
-    const Geometry g = geometry(args.img[i].H, args.img[i].W, args.img[i].mode);
+    const Geometry g = geometry<true>(args.img[i].H, args.img[i].W, args.img[i].mode);
     args.img[i].plane_off = (i64)at;
     at += (size_t)g.pw0 * g.ph0 + 2 * (size_t)g.pw1 * g.ph1;
+  }
+  if (cam) {
+    *cam = {};
+    for (int i = 0; i < n; ++i) {
+      const Geometry g = geometry<true>(args.img[i].H, args.img[i].W, args.img[i].mode);
+      CamImage &C = cam->img[i];
+      const int nm = g.mw * g.mh;
+      C.interval = jobs[i].reserved;
+      C.nint = C.interval ? ceil_div(nm, C.interval) : 1;
+      C.per_tile = (int)std::min<i64>(std::max<i64>((i64)C.nint * kTileBytes / args.img[i].scan_bytes, 1), kLanes);
+      C.ntiles = ceil_div(C.nint, C.per_tile);
+      L.most_tiles = std::max(L.most_tiles, C.ntiles);
+      at = align_up(at, 16);
+      C.table_off = (i64)at;
+      at += align_up(12 * ((size_t)C.nint + 1), 16);
+      C.tile_off = (i64)at;
+      at += align_up(8 * (size_t)C.ntiles, 16);
+    }
   }
   L.total = at;
   return KGDET_OK;
@@ -655,9 +1056,14 @@ int kgdet_jpeg_decode(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_de
   return kgdet_jpeg_decode_stages(src, src_bytes, jobs, n, workspace, workspace_bytes, out, out_bytes, status, stream, 4);
 }
 
-int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
-                             size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream,
-                             int32_t stages) {
+}  // extern "C"
+
+namespace kgdet {
+namespace {
+
+// the body of kgdet_jpeg_decode_stages and kgdet_jpeg_decode_camera_stages
+int run(bool camera, const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
+        size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream, int32_t stages) {
   KGDET_CHECK_SHAPE(stages >= 1 && stages <= 4, "jpeg_decode: %d stages (1 .. 4)", stages);
   KGDET_CHECK_SHAPE(n >= 0 && n <= kMaxImages, "jpeg_decode: %d images in one call (0 .. %d)", n, kMaxImages);
   KGDET_CHECK_SHAPE(src_bytes >= 0 && out_bytes >= 0, "jpeg_decode: negative size");
@@ -665,8 +1071,10 @@ int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_
   KGDET_CHECK_SHAPE(src && jobs && workspace && out && status, "jpeg_decode: null pointer");
   KGDET_CHECK_SHAPE(((uintptr_t)workspace & 15u) == 0, "jpeg_decode: the workspace is not 16-byte aligned");
   DecArgs args;
+  CamArgs cam;
   Layout L;
-  if (int rc = plan("jpeg_decode", jobs, n, src_bytes, out_bytes, args, L)) return rc;
+  if (int rc = plan(camera ? "jpeg_decode_camera" : "jpeg_decode", jobs, n, src_bytes, out_bytes, args, L, camera ? &cam : nullptr))
+    return rc;
   KGDET_CHECK_SHAPE(workspace_bytes >= L.total, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
   KGDET_CHECK_SHAPE(disjoint(src, (uint64_t)src_bytes, workspace, workspace_bytes) &&
                         disjoint(src, (uint64_t)src_bytes, out, (uint64_t)out_bytes) &&
@@ -683,30 +1091,83 @@ int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_
     KGDET_HIP_TRY(hipMemsetAsync(status, 0xFF, 4 * (size_t)n, s));
     return KGDET_OK;
   };
-  hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, args, (const u8 *)src, ws, lens, (int *)status);
-  KGDET_CHECK_LAUNCH("jpeg_unstuff_kernel");
+  if (camera) {
+    hipLaunchKernelGGL(jpeg_unstuff_camera_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, args, cam, (const u8 *)src, ws, lens,
+                       (int *)status);
+    KGDET_CHECK_LAUNCH("jpeg_unstuff_camera_kernel");
+  } else {
+    hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, args, (const u8 *)src, ws, lens, (int *)status);
+    KGDET_CHECK_LAUNCH("jpeg_unstuff_kernel");
+  }
   if (stop <= 1) return stopped();
   KGDET_HIP_TRY(hipMemsetAsync(ws + L.coef, 0, L.coef_bytes, s));
-  hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, args, (const u8 *)src, ws, (const u32 *)lens,
-                     lens + kMaxImages, (int *)status);
-  KGDET_CHECK_LAUNCH("jpeg_huffman_kernel");
+  if (camera) {
+    hipLaunchKernelGGL(jpeg_huffman_camera_kernel, dim3((unsigned)L.most_tiles, (unsigned)n), dim3(kLanes), 0, s, args, cam,
+                       (const u8 *)src, ws, (const int *)status);
+    KGDET_CHECK_LAUNCH("jpeg_huffman_camera_kernel");
+    hipLaunchKernelGGL(jpeg_verdict_camera_kernel, dim3((unsigned)n), dim3(kBackThreads), 0, s, cam, (const u8 *)ws,
+                       lens + kMaxImages, (int *)status);
+    KGDET_CHECK_LAUNCH("jpeg_verdict_camera_kernel");
+  } else {
+    hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, args, (const u8 *)src, ws, (const u32 *)lens,
+                       lens + kMaxImages, (int *)status);
+    KGDET_CHECK_LAUNCH("jpeg_huffman_kernel");
+  }
   if (stop <= 2) return stopped();
   int most_blocks = 1;
   i64 most_pieces = 1;
   for (int i = 0; i < n; ++i) {
-    most_blocks = std::max(most_blocks, geometry(args.img[i].H, args.img[i].W, args.img[i].mode).nblocks);
+    most_blocks = std::max(most_blocks, geometry<true>(args.img[i].H, args.img[i].W, args.img[i].mode).nblocks);
     most_pieces = std::max(most_pieces, (3ll * args.img[i].H * args.img[i].W + 30) / 16);
   }
   const int cap = std::max(1, 8 * cu_count() / n);
-  hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)std::min(ceil_div(most_blocks, kBackThreads), cap), (unsigned)n),
-                     dim3(kBackThreads), 0, s, args, (const u8 *)src, ws, (const int *)status);
+  const dim3 idct_grid((unsigned)std::min(ceil_div(most_blocks, kBackThreads), cap), (unsigned)n);
+  if (camera)
+    hipLaunchKernelGGL(jpeg_idct_kernel<true>, idct_grid, dim3(kBackThreads), 0, s, args, (const u8 *)src, ws, (const int *)status);
+  else
+    hipLaunchKernelGGL(jpeg_idct_kernel<false>, idct_grid, dim3(kBackThreads), 0, s, args, (const u8 *)src, ws, (const int *)status);
   KGDET_CHECK_LAUNCH("jpeg_idct_kernel");
   if (stop <= 3) return stopped();
-  hipLaunchKernelGGL(jpeg_colour_kernel,
-                     dim3((unsigned)std::min<i64>((most_pieces + kBackThreads - 1) / kBackThreads, (i64)cap), (unsigned)n),
-                     dim3(kBackThreads), 0, s, args, (const u8 *)ws, (u8 *)out, (const int *)status);
+  const dim3 colour_grid((unsigned)std::min<i64>((most_pieces + kBackThreads - 1) / kBackThreads, (i64)cap), (unsigned)n);
+  if (camera)
+    hipLaunchKernelGGL(jpeg_colour_kernel<true>, colour_grid, dim3(kBackThreads), 0, s, args, (const u8 *)ws, (u8 *)out,
+                       (const int *)status);
+  else
+    hipLaunchKernelGGL(jpeg_colour_kernel<false>, colour_grid, dim3(kBackThreads), 0, s, args, (const u8 *)ws, (u8 *)out,
+                       (const int *)status);
   KGDET_CHECK_LAUNCH("jpeg_colour_kernel");
   return KGDET_OK;
+}
+
+}  // namespace
+}  // namespace kgdet
+
+extern "C" {
+
+int kgdet_jpeg_decode_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
+                             size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream,
+                             int32_t stages) {
+  return run(false, src, src_bytes, jobs, n, workspace, workspace_bytes, out, out_bytes, status, stream, stages);
+}
+
+size_t kgdet_jpeg_decode_camera_workspace_bytes(const kgdet_jpeg_decode_job *jobs, int32_t n) {
+  if (n < 0 || n > kMaxImages || (n > 0 && !jobs)) return 0;
+  DecArgs args;
+  CamArgs cam;
+  Layout L;
+  if (plan("jpeg_decode_camera_workspace_bytes", jobs, n, -1, -1, args, L, &cam) != KGDET_OK) return 0;
+  return L.total;
+}
+
+int kgdet_jpeg_decode_camera(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n, void *workspace,
+                             size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status, void *stream) {
+  return run(true, src, src_bytes, jobs, n, workspace, workspace_bytes, out, out_bytes, status, stream, 4);
+}
+
+int kgdet_jpeg_decode_camera_stages(const uint8_t *src, int64_t src_bytes, const kgdet_jpeg_decode_job *jobs, int32_t n,
+                                    void *workspace, size_t workspace_bytes, uint8_t *out, int64_t out_bytes, int32_t *status,
+                                    void *stream, int32_t stages) {
+  return run(true, src, src_bytes, jobs, n, workspace, workspace_bytes, out, out_bytes, status, stream, stages);
 }
 
 }  // extern "C"

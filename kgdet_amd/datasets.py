@@ -208,16 +208,17 @@ class DeepFashion2Dataset(object):
         with Image.open(os.path.join(self.img_prefix, self.img_infos[idx]['filename'])) as im:
             return np.array(im.convert('RGB'))
 
-    def load_image_file(self, idx):
+    def load_image_file(self, idx, camera=False):
         """the image's FILE for the device decoder (``jpeg.DeviceDecodeRoute``): an ``EncodedImage`` with the file's bytes and
         ``shape`` = (H, W, 3) from its header.  A file the decoder does not take (``jpeg.parse_header``'s ``reason``) is decoded
         with PIL right here -- on the thread that read it, with one warning per file that names it and the reason -- and carried as
-        ``pixels``: the bits ``load_image`` returns."""
+        ``pixels``: the bits ``load_image`` returns.  ``camera``: ``jpeg.parse_header``'s switch, that of the loop's
+        ``device_decode='camera'``."""
         from . import jpeg
         name = os.path.join(self.img_prefix, self.img_infos[idx]['filename'])
         with open(name, 'rb') as f:
             data = f.read()
-        frame = jpeg.parse_header(data)
+        frame = jpeg.parse_header(data, camera)
         if isinstance(frame, str):
             warned = self.__dict__.setdefault('_decode_warned', set())
             if name not in warned:                   # (once per file, not once per epoch)

@@ -385,7 +385,10 @@ DECODE_SUBSEQ_BITS = 512    # KGDET_JPEG_DECODE_SUBSEQ_BITS: bits of the un-stuf
 DECODE_CHUNK_LANES = 1024   # KGDET_JPEG_DECODE_CHUNK_LANES: subsequences a workgroup brings to their fixpoint together
 DECODE_TABLE_BYTES = 1024   # KGDET_JPEG_DECODE_TABLE_BYTES: the table block of one image inside the source buffer
 MODE_GREY, MODE_444, MODE_420 = 0, 1, 2         # KGDET_JPEG_DECODE_GREY / _444 / _420
-BLOCKS_PER_MCU = (1, 3, 6)
+MODE_422 = 3                                    # KGDET_JPEG_DECODE_422: the ``camera`` entry points only
+BLOCKS_PER_MCU = (1, 3, 6, 4)
+SLOT_COMPONENT = ((0,), (0, 1, 2), (0, 0, 0, 0, 1, 2), (0, 0, 1, 2))     # the component of each block slot of the MCU, by mode
+MAX_RESTART_INTERVAL = 65535
 INVALID = (-1, -1, -1)      # the state of a parse that met an unmatched code or left the block: equal to no valid state
 
 IDCT_CONST = dict(c0_298=2446, c0_390=3196, c0_541=4433, c0_765=6270, c0_899=7373, c1_175=9633, c1_501=12299, c1_847=15137,
@@ -402,7 +405,7 @@ def _kraft_ok(bits):
     return True
 
 
-def parse_header(data):
+def parse_header(data, camera=False):
     """Walk the segments of a JPEG file up to the end of ``SOS`` (segment lengths only; no entropy byte is touched) -> the frame
     description the decoder needs, or a REASON STRING (in the style of ``head_loss.why_not``) for a file it does not take.
 
@@ -413,13 +416,18 @@ def parse_header(data):
     restart interval, ``APP14`` Adobe, 16-bit tables, four components, H = 0 (``DNL``), more than one scan -- gives its reason.
 
     The description: dict(H, W, ncomp, mode, qt uint8 [3, 64] natural order per component, dc / ac {id: (bits, vals)},
-    comp_dc / comp_ac [3], scan_offset, tables = the ``DECODE_TABLE_BYTES`` block ``kgdet_jpeg_decode`` reads)."""
+    comp_dc / comp_ac [3], scan_offset, tables = the ``DECODE_TABLE_BYTES`` block ``kgdet_jpeg_decode`` reads).
+
+    ``camera=True`` (the files cameras and phones write; ``kgdet_jpeg_decode_camera``) additionally takes three components
+    sampled 2x1 / 1x1 / 1x1 (4:2:2, ``MODE_422``: an MCU is 16 wide and 8 high, its blocks Y left, Y right, Cb, Cr) and a ``DRI``
+    with a non-zero interval; the description then carries ``restart_interval`` (MCUs, 0: none).  Everything else keeps its
+    reason, and without the switch the result is what it was."""
     data = bytes(data)
     if data[:2] != b'\xff\xd8':
         return 'no SOI marker'
     at, size = 2, len(data)
     qt, dc, ac = {}, {}, {}
-    sof, jfif = None, False
+    sof, jfif, restart = None, False, 0
     while True:
         if at + 4 > size:
             return 'the file ends inside its header'
@@ -484,8 +492,9 @@ def parse_header(data):
         elif marker == 0xDD:
             if n != 4:
                 return 'malformed DRI segment'
-            if body[0] << 8 | body[1]:
-                return 'restart interval %d (DRI)' % (body[0] << 8 | body[1])
+            restart = body[0] << 8 | body[1]
+            if restart and not camera:
+                return 'restart interval %d (DRI)' % restart
         elif marker == 0xDC:
             return 'DNL segment'
         elif marker == 0xDA:
@@ -513,6 +522,8 @@ def parse_header(data):
         mode = MODE_420
     elif sampling == [(1, 1), (1, 1), (1, 1)]:
         mode = MODE_444
+    elif camera and sampling == [(2, 1), (1, 1), (1, 1)]:
+        mode = MODE_422
     else:
         return 'sampling %s (2x2 / 1x1 / 1x1 and 1x1 / 1x1 / 1x1 are read)' % ' / '.join('%dx%d' % s for s in sampling)
     if len(comps) == 3 and not (jfif or [c[0] for c in comps] == [1, 2, 3]):
@@ -543,14 +554,18 @@ def parse_header(data):
                 blob[bits_at + 16 * t:bits_at + 16 * t + 16] = bytes(bits)
                 blob[vals_at + room * t:vals_at + room * t + len(vals)] = bytes(vals)
     blob[800:803], blob[803:806] = bytes(comp_dc), bytes(comp_ac)
-    return dict(H=H, W=W, ncomp=len(comps), mode=mode, qt=Q, dc=dc, ac=ac, comp_dc=comp_dc, comp_ac=comp_ac,
-                scan_offset=at + 2 + n, tables=bytes(blob))
+    frame = dict(H=H, W=W, ncomp=len(comps), mode=mode, qt=Q, dc=dc, ac=ac, comp_dc=comp_dc, comp_ac=comp_ac,
+                 scan_offset=at + 2 + n, tables=bytes(blob))
+    if camera:
+        frame['restart_interval'] = restart
+    return frame
 
 
 def frame_blocks(frame):
     """(MCUs per row, MCU rows, blocks per MCU) of a frame; a one-component scan is not padded to an MCU: its MCU is a block"""
-    unit = 16 if frame['mode'] == MODE_420 else 8
-    return (frame['W'] + unit - 1) // unit, (frame['H'] + unit - 1) // unit, BLOCKS_PER_MCU[frame['mode']]
+    wide = 16 if frame['mode'] in (MODE_420, MODE_422) else 8
+    high = 16 if frame['mode'] == MODE_420 else 8
+    return (frame['W'] + wide - 1) // wide, (frame['H'] + high - 1) // high, BLOCKS_PER_MCU[frame['mode']]
 
 
 def unstuff(data, scan_offset):
@@ -564,6 +579,26 @@ def unstuff(data, scan_offset):
     if data[k + 1] != 0xD9:
         raise ValueError('marker %02X ends the scan, not EOI' % data[k + 1])
     return data[scan_offset:k].replace(b'\xff\x00', b'\xff')
+
+
+def unstuff_intervals(data, scan_offset):
+    """``unstuff`` for a scan with restart intervals: the scan's data is cut at every 0xFF 0xD0+m and each piece is un-stuffed
+    on its own -> (the pieces, the marker numbers m in file order).  The scan ends at the first 0xFF that neither 0x00 nor a
+    restart marker follows (a second 0xFF included: no fill bytes here), which has to be ``EOI``."""
+    pieces, markers, at = [], [], scan_offset
+    k = data.find(b'\xff', scan_offset)
+    while k >= 0 and k + 1 < len(data) and (data[k + 1] == 0 or 0xD0 <= data[k + 1] <= 0xD7):
+        if data[k + 1]:
+            pieces.append(data[at:k].replace(b'\xff\x00', b'\xff'))
+            markers.append(data[k + 1] - 0xD0)
+            at = k + 2
+        k = data.find(b'\xff', k + 2)
+    if k < 0 or k + 1 >= len(data):
+        raise ValueError('no marker ends the scan')
+    if data[k + 1] != 0xD9:
+        raise ValueError('marker %02X ends the scan, not EOI' % data[k + 1])
+    pieces.append(data[at:k].replace(b'\xff\x00', b'\xff'))
+    return pieces, markers
 
 
 def _lookup(bits, vals):
@@ -584,7 +619,8 @@ class EntropyContext(object):
     """the un-stuffed stream of a file with what ``decode_span`` needs: ``window[p]`` = the 32 bits from bit p (1-bits behind the
     end), the look-ups of each block slot of the MCU, ``total_bits``"""
 
-    def __init__(self, frame, stream):
+    def __init__(self, frame, stream, tables=None):
+        """``tables``: a context of the same frame whose look-ups are shared (the intervals of one file)"""
         self.frame, self.stream, self.total_bits = frame, stream, 8 * len(stream)
         bit = np.unpackbits(np.frombuffer(stream + b'\xff' * 5, dtype=np.uint8)).astype(np.int64)
         window = np.zeros(self.total_bits + 1, dtype=np.int64)
@@ -592,7 +628,10 @@ class EntropyContext(object):
             window += bit[j:j + self.total_bits + 1] << (31 - j)
         self.window = window.tolist()
         self.bpm = BLOCKS_PER_MCU[frame['mode']]
-        comp = {MODE_GREY: (0,), MODE_444: (0, 1, 2), MODE_420: (0, 0, 0, 0, 1, 2)}[frame['mode']]
+        comp = SLOT_COMPONENT[frame['mode']]
+        if tables is not None:
+            self.slot_comp, self.slot_tables = tables.slot_comp, tables.slot_tables
+            return
         luts = {}
         for kind, tables in (('dc', frame['dc']), ('ac', frame['ac'])):
             for t, (bits, vals) in tables.items():
@@ -704,6 +743,17 @@ def idct_blocks(levels, q):
     return np.clip(out, 0, 255).transpose(0, 2, 1, 3).reshape(8 * a, 8 * b)
 
 
+def fancy_upsample_h2v1(c, cw):
+    """libjpeg's triangle ("fancy") h2v1 upsampling of the real extent ``cw`` of a chroma plane's rows -> int64 [rows, 2 cw]"""
+    c = c[:, :cw].astype(np.int64)
+    if cw <= 2:                         # libjpeg replicates a plane of up to two samples a row (at cw = 1 the same values)
+        return np.repeat(c, 2, axis=1)
+    left, right = np.concatenate([c[:, :1], c[:, :-1]], 1), np.concatenate([c[:, 1:], c[:, -1:]], 1)
+    out = np.empty((c.shape[0], 2 * cw), dtype=np.int64)
+    out[:, 0::2], out[:, 1::2] = (3 * c + left + 1) >> 2, (3 * c + right + 2) >> 2
+    return out
+
+
 def fancy_upsample(c, ch, cw):
     """libjpeg's triangle ("fancy") h2v2 upsampling of the real extent [ch, cw] of a chroma plane -> int64 [2 ch, 2 cw]"""
     c = c[:ch, :cw].astype(np.int64)
@@ -716,31 +766,52 @@ def fancy_upsample(c, ch, cw):
     return out
 
 
-def decode_parts(data, trace=None):
+def decode_parts(data, trace=None, camera=False):
     """the restatement with its intermediate results: dict(frame, stream, coefficients int64 [blocks, 64] natural order in
-    scan order with the DC values summed, planes, image)"""
+    scan order with the DC values summed, planes, image); ``camera``: ``parse_header``'s switch (``stream`` is then the
+    intervals' un-stuffed bytes one after the other and ``intervals`` their lengths)"""
     data = bytes(data)
-    frame = parse_header(data)
+    frame = parse_header(data, camera)
     if isinstance(frame, str):
         raise ValueError('decode_restatement does not read this file: %s' % frame)
-    stream = unstuff(data, frame['scan_offset'])
-    ctx = EntropyContext(frame, stream)
     mw, mh, bpm = frame_blocks(frame)
     nblocks = mw * mh * bpm
     zz = np.zeros((nblocks + 1, 64), dtype=np.int64)
+    interval = frame.get('restart_interval', 0)
+    if interval:
+        pieces, markers = unstuff_intervals(data, frame['scan_offset'])
+        count = -(-mw * mh // interval)
+        if len(pieces) != count:
+            raise ValueError('%d restart markers in a scan of %d intervals' % (len(markers), count))
+        if markers != [m % 8 for m in range(count - 1)]:
+            raise ValueError('the restart markers do not count 0 .. 7 in turn: %s' % markers)
+    else:
+        pieces = [unstuff(data, frame['scan_offset'])]
+    stream = b''.join(pieces)
+    ctx, first = None, 0
+    for k, piece in enumerate(pieces):
+        ctx = EntropyContext(frame, piece, ctx)
+        share = min(nblocks - first, interval * bpm) if interval else nblocks
 
-    def sink(block, place, value):
-        zz[min(block, nblocks), place] = value
-    state, done = decode_span(ctx, (0, 0, 0), ctx.total_bits, sink, trace)
-    if state == INVALID:
-        raise ValueError('the scan holds an invalid code')
-    if done != nblocks or state[2] != 0 or not 0 <= ctx.total_bits - state[0] < 8:
-        raise ValueError('the scan holds %d blocks and ends %d bits before its data does; the frame has %d blocks'
-                         % (done, ctx.total_bits - state[0], nblocks))
+        def sink(block, place, value):
+            zz[first + block if block < share else nblocks, place] = value
+        state, done = decode_span(ctx, (0, 0, 0), ctx.total_bits, sink, trace)
+        if state == INVALID:
+            raise ValueError('the scan holds an invalid code')
+        if done != share or state[2] != 0 or not 0 <= ctx.total_bits - state[0] < 8:
+            if interval:
+                raise ValueError('interval %d holds %d blocks and ends %d bits before its data does; its share is %d blocks'
+                                 % (k, done, ctx.total_bits - state[0], share))
+            raise ValueError('the scan holds %d blocks and ends %d bits before its data does; the frame has %d blocks'
+                             % (done, ctx.total_bits - state[0], nblocks))
+        first += share
+    ctx = EntropyContext(frame, stream, ctx) if interval else ctx
     zz = zz[:nblocks].reshape(mw * mh, bpm, 64)
-    for slots in {MODE_GREY: ((0,),), MODE_444: ((0,), (1,), (2,)), MODE_420: ((0, 1, 2, 3), (4,), (5,))}[frame['mode']]:
-        dc = zz[:, slots, 0]
-        zz[:, slots, 0] = np.cumsum(dc.reshape(-1)).reshape(dc.shape)
+    comp = np.array(SLOT_COMPONENT[frame['mode']])
+    for at in range(0, mw * mh, interval or mw * mh):                           # the running sums start at 0 in every interval
+        for c in range(frame['ncomp']):
+            dc = zz[at:at + (interval or mw * mh), comp == c, 0]
+            zz[at:at + (interval or mw * mh), comp == c, 0] = np.cumsum(dc.reshape(-1)).reshape(dc.shape)
     zz = np.clip(zz, -32768, 32767)
     coef = np.zeros_like(zz)
     coef[..., ZIGZAG] = zz
@@ -751,6 +822,10 @@ def decode_parts(data, trace=None):
         ch, cw = (H + 1) // 2, (W + 1) // 2
         planes = [idct_blocks(luma, Q[0])[:H, :W]] + [fancy_upsample(idct_blocks(grid[:, :, 3 + c], Q[c]), ch, cw)[:H, :W]
                                                      for c in (1, 2)]
+    elif frame['mode'] == MODE_422:
+        luma = grid[:, :, :2].reshape(mh, 2 * mw, 8, 8)
+        planes = [idct_blocks(luma, Q[0])[:H, :W]] + [fancy_upsample_h2v1(idct_blocks(grid[:, :, 1 + c], Q[c]), (W + 1) // 2)[:H, :W]
+                                                     for c in (1, 2)]
     else:
         planes = [idct_blocks(grid[:, :, c], Q[c])[:H, :W] for c in range(bpm)]
     if frame['mode'] == MODE_GREY:
@@ -760,10 +835,13 @@ def decode_parts(data, trace=None):
         rgb = np.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16),
                         Y + ((116130 * cb + 32768) >> 16)], -1)
     image = np.clip(rgb, 0, 255).astype(np.uint8)
-    return dict(frame=frame, stream=stream, context=ctx, coefficients=coef.reshape(nblocks, 64), planes=planes, image=image)
+    out = dict(frame=frame, stream=stream, context=ctx, coefficients=coef.reshape(nblocks, 64), planes=planes, image=image)
+    if camera:
+        out['intervals'] = [len(piece) for piece in pieces]
+    return out
 
 
-def decode_restatement(data):
+def decode_restatement(data, camera=False):
     """The picture of a JPEG file ``parse_header`` takes -> uint8 [H, W, 3] RGB: the definition ``kgdet_jpeg_decode`` is held to
     bit for bit, itself held to PIL's decoder (libjpeg-turbo), which is what ``DeepFashion2Dataset.load_image`` returns.
 
@@ -782,8 +860,19 @@ def decode_restatement(data):
     Pinned domain: equality with PIL holds for files an encoder made from pixels (tests/test_jpeg_decode_refs.py).  A patched
     file whose dequantised coefficients overflow 16-bit intermediates is outside it: libjpeg-turbo's SIMD inverse DCT wraps
     there, where this definition (64-bit integers) and the kernels clamp and agree with each other.  Raises ``ValueError``
-    for a file ``parse_header`` refuses and for a scan that is malformed; PIL is more lenient with both."""
-    return decode_parts(data)['image']
+    for a file ``parse_header`` refuses and for a scan that is malformed; PIL is more lenient with both.
+
+    ``camera=True`` (``parse_header``'s switch; ``kgdet_jpeg_decode_camera``'s definition):
+    - Restart intervals.  The scan's data is cut at every 0xFF 0xD0+m (``unstuff_intervals``); the markers must count m = 0, 1,
+      .. 7, 0, .. and there are exactly ceil(MCUs / interval) - 1 of them before ``EOI``.  Each piece is un-stuffed on its own
+      and decoded by ``decode_span`` from (0, 0, 0); it has to hold exactly its share of blocks (interval * blocks per MCU, the
+      last piece the remainder) and end within the last byte of its data; the DC running sums start at 0 in every piece.  The
+      look-ups are built once per file.  A violation is a ``ValueError``.
+    - 4:2:2 chroma: libjpeg's h2v1 "fancy" upsampling over the real extent ceil(W / 2): out[2x] = (3 c[x] + c[x - 1] + 1) >> 2,
+      out[2x + 1] = (3 c[x] + c[x + 1] + 2) >> 2, the neighbour replicated at both edges; rows are not touched.  A plane of
+      two samples a row (W = 3, 4) is replicated instead, out[2x] = out[2x + 1] = c[x], as libjpeg does for widths up to 2.
+      The luma grid is the MCU's two blocks side by side.  Steps 2, 3 and 5 are unchanged."""
+    return decode_parts(data, camera=camera)['image']
 
 
 def _align(v, a):
@@ -813,11 +902,15 @@ class DeviceJpegDecoder(object):
     needs the pictures.  The files travel through one page-locked staging copy and one non-blocking upload, as
     ``DeviceImageTransform._upload``'s images do; everything runs on the device's current stream.  The workspace grows to the
     largest group seen (about 3.5 bytes per pixel of a 4:2:0 picture) and is reused: every call makes its stream wait for the
-    event behind the previous call, so the object may be used from any stream (one thread at a time)."""
+    event behind the previous call, so the object may be used from any stream (one thread at a time).
 
-    def __init__(self, device=None):
+    ``camera=True``: ``kgdet_jpeg_decode_camera`` and ``parse_header(camera=True)``'s files -- 4:2:2 and restart intervals as
+    well, bit for bit ``decode_restatement(camera=True)``'s; status 4 (``KGDET_JPEG_DECODE_BAD_RESTART``) joins the verdicts."""
+
+    def __init__(self, device=None, camera=False):
         import torch
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.camera = bool(camera)
         self.workspace = None
         self._pinned = None
         self._pinned_free = None
@@ -827,7 +920,7 @@ class DeviceJpegDecoder(object):
     def __call__(self, files, frames=None):
         import torch
         files = [bytes(f) for f in files]
-        frames = [parse_header(f) for f in files] if frames is None else list(frames)
+        frames = [parse_header(f, self.camera) for f in files] if frames is None else list(frames)
         for k, frame in enumerate(frames):
             if isinstance(frame, str):
                 raise ValueError('file %d is not one the device decodes: %s' % (k, frame))
@@ -845,12 +938,13 @@ class DeviceJpegDecoder(object):
             self._pinned_free = torch.cuda.Event()
             self._pinned_free.record()
         self.uploaded += total
-        jobs = [(so, sb, to, f['H'], f['W'], f['mode']) for (so, sb, to), f in zip(places, frames)]
+        jobs = [(so, sb, to, f['H'], f['W'], f['mode'], f.get('restart_interval', 0)) for (so, sb, to), f in zip(places, frames)]
         return self.decode(src, jobs)
 
     def decode(self, src, jobs, out=None, stages=4):
         """the files' bytes already on the device: ``src`` a flat uint8 device tensor, ``jobs`` [(scan offset, scan bytes,
-        tables offset, H, W, mode)] with the offsets inside ``src`` -> ``(images, status)``; ``out``: a flat uint8 device tensor
+        tables offset, H, W, mode[, restart interval])] with the offsets inside ``src`` (an interval or ``MODE_422`` needs
+        ``camera=True``) -> ``(images, status)``; ``out``: a flat uint8 device tensor
         to decode into (the pictures follow each other at multiples of 256 bytes).  ``stages`` < 4 (the timing tool's): only
         the first kernels run, no picture is made and every status is -1.  The workspace is shared by the object's calls: a
         call waits, on the device, for the previous one, whichever stream that ran on."""
@@ -859,8 +953,13 @@ class DeviceJpegDecoder(object):
         from . import _lib
         lib, p = _lib.lib(), _lib.ptr
         dev = src.device
+        jobs = [tuple(j) + (0,) * (7 - len(j)) for j in jobs]
+        if not self.camera and any(j[5] == MODE_422 or j[6] for j in jobs):
+            raise ValueError('a 4:2:2 file or a restart interval needs DeviceJpegDecoder(camera=True)')
+        name = 'kgdet_jpeg_decode_camera' if self.camera else 'kgdet_jpeg_decode'
+        workspace_bytes, decode_stages = getattr(lib, name + '_workspace_bytes'), getattr(lib, name + '_stages')
         places, total = [], 0
-        for _, _, _, H, W, _ in jobs:
+        for _, _, _, H, W, _, _ in jobs:
             places.append(total)
             total += _align(3 * H * W, 256)
         if out is None:
@@ -875,23 +974,22 @@ class DeviceJpegDecoder(object):
             for g in range(0, len(jobs), DECODE_MAX_IMAGES):
                 group = jobs[g:g + DECODE_MAX_IMAGES]
                 table = (_lib.JpegDecodeJob * len(group))(*[
-                    _lib.JpegDecodeJob(int(so), int(sb), int(to), places[g + k], int(H), int(W), int(mode), 0)
-                    for k, (so, sb, to, H, W, mode) in enumerate(group)])
+                    _lib.JpegDecodeJob(int(so), int(sb), int(to), places[g + k], int(H), int(W), int(mode), int(interval))
+                    for k, (so, sb, to, H, W, mode, interval) in enumerate(group)])
                 n = ctypes.c_int32(len(group))
-                need = lib.kgdet_jpeg_decode_workspace_bytes(table, n)
+                need = workspace_bytes(table, n)
                 if need == 0:
-                    _lib.check(_lib.KGDET_E_SHAPE, 'kgdet_jpeg_decode_workspace_bytes')
+                    _lib.check(_lib.KGDET_E_SHAPE, name + '_workspace_bytes')
                 if self.workspace is None or self.workspace.numel() < need or self.workspace.device != dev:
                     self.workspace = None
                     self.workspace = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
                 ws = self.workspace
-                _lib.check(lib.kgdet_jpeg_decode_stages(p(src), ctypes.c_int64(src.numel()), table, n, p(ws),
-                                                        ctypes.c_size_t(ws.numel()), p(out), ctypes.c_int64(out.numel()),
-                                                        p(status[g:g + len(group)]), stream, ctypes.c_int32(stages)),
-                           'kgdet_jpeg_decode')
+                _lib.check(decode_stages(p(src), ctypes.c_int64(src.numel()), table, n, p(ws), ctypes.c_size_t(ws.numel()), p(out),
+                                         ctypes.c_int64(out.numel()), p(status[g:g + len(group)]), stream, ctypes.c_int32(stages)),
+                           name)
             self._last = torch.cuda.Event()
             self._last.record()
-        images = [out[at:at + 3 * H * W].view(H, W, 3) for at, (_, _, _, H, W, _) in zip(places, jobs)]
+        images = [out[at:at + 3 * H * W].view(H, W, 3) for at, (_, _, _, H, W, _, _) in zip(places, jobs)]
         return images, status
 
     def rounds(self, n):
@@ -911,18 +1009,28 @@ def decode_pil(data):
 _decoders = {}
 
 
-def decode_jpeg(data):
+def decode_switch(device_decode):
+    """what the loops' ``device_decode`` asks for -> (decode on the device, the ``camera`` switch): False / None, True (the
+    baseline files), or 'camera' (4:2:2 files and restart intervals as well)"""
+    if device_decode == 'camera':
+        return True, True
+    if isinstance(device_decode, str):
+        raise ValueError("device_decode is False, True or 'camera', got %r" % (device_decode,))
+    return bool(device_decode), False           # (any other value by its truth, as before the switch)
+
+
+def decode_jpeg(data, camera=False):
     """the picture of a JPEG file -> uint8 [H, W, 3] RGB numpy array: by ``DeviceJpegDecoder`` when a GPU and the library are
     there, ``parse_header`` takes the file and the kernels' status is 0; else by PIL.  On the pinned domain (see
-    ``decode_restatement``) both give the same bits."""
+    ``decode_restatement``) both give the same bits.  ``camera``: ``parse_header``'s switch."""
     import torch
     data = bytes(data)
     if device_available():
-        frame = parse_header(data)
+        frame = parse_header(data, camera)
         if not isinstance(frame, str):
-            dev = torch.cuda.current_device()
+            dev = (torch.cuda.current_device(), bool(camera))
             if dev not in _decoders:
-                _decoders[dev] = DeviceJpegDecoder(torch.device('cuda', dev))
+                _decoders[dev] = DeviceJpegDecoder(torch.device('cuda', dev[0]), camera)
             images, status = _decoders[dev]([data], [frame])
             if int(status[0]) == 0:
                 return images[0].cpu().numpy()
@@ -941,12 +1049,15 @@ class DeviceDecodeRoute(object):
     for the decode's event, and the pictures are marked as used on it (``record_stream``).  ``start_block`` / ``finish_block``: the same in two halves for files
     that already lie in a page-locked block (the loader's ring slot, ``pack_files``' layout at ``files_at``), which goes up in
     one copy together with whatever else the block holds; it returns the device block too.  Between the halves nothing is waited for, so the loader
-    starts the next batch's decode while the consumer trains on this one."""
+    starts the next batch's decode while the consumer trains on this one.
 
-    def __init__(self, device=None):
+    ``camera=True``: the samples' frames come from ``parse_header(camera=True)`` (``load_image_file(idx, camera=True)``) and
+    the route decodes with ``kgdet_jpeg_decode_camera``."""
+
+    def __init__(self, device=None, camera=False):
         import torch
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        self.decoder = DeviceJpegDecoder(self.device)
+        self.decoder = DeviceJpegDecoder(self.device, camera)
         self.stream = None
         self._status = None
         self._turn = 0
@@ -993,8 +1104,8 @@ class DeviceDecodeRoute(object):
                 uploaded.record()
                 images, done, slot = [], None, self._turn
                 if which:
-                    jobs = [(files_at + so, sb, files_at + to, raws[k].frame['H'], raws[k].frame['W'], raws[k].frame['mode'])
-                            for k, (so, sb, to) in zip(which, places)]
+                    jobs = [(files_at + so, sb, files_at + to, raws[k].frame['H'], raws[k].frame['W'], raws[k].frame['mode'],
+                             raws[k].frame.get('restart_interval', 0)) for k, (so, sb, to) in zip(which, places)]
                     images, status = self.decoder.decode(dev, jobs)
                     self._turn = 1 - slot                # (two handles may be open: each has its own page-locked status)
                     done = self._read_back(status, slot)

@@ -47,9 +47,12 @@ step queued on the consumer's stream; that stream then waits for the decode's ev
 staged as a batch is handed out, its upload and decode are issued right then (one batch ahead, nothing waited for), so they run
 under the training step and the next ``__next__`` should find the status there (measured, README: it still waits 4 to 5 ms
 per batch, against 1.3 to 2.9 ms of the threaded PIL route -- the decode call is slower under the step).  A file the decoder does not take
-(progressive, 4:2:2, ...) is decoded by PIL in the pool, as on the other routes.  The resample of an image without annotations
+(progressive, 4:2:2, ...) is decoded by PIL in the pool, as on the other routes.  ``device_decode='camera'`` is the same route
+with ``jpeg.parse_header(camera=True)`` and ``kgdet_jpeg_decode_camera``: 4:2:2 files and files with restart intervals are
+decoded on the device too, without a warning; the rest of that list still goes to PIL.  The resample of an image without annotations
 reads that image's file on the drawing thread (the other routes decode it there) and it is decoded on the GPU with its batch.
 """
+import functools
 import threading
 import weakref
 from concurrent.futures import ThreadPoolExecutor
@@ -163,7 +166,7 @@ class _Epoch(object):
         self.dataset, self.B, self.prefetch = loader.dataset, loader.batch_size, max(loader.prefetch, 1)
         self.workers, self.raw_route, self.staged = loader.workers, loader.device_preprocess, loader.device is not None
         self.decode = loader.device_decode
-        self.load = loader.dataset.load_image_file if self.decode else loader.dataset.load_image
+        self.load = loader._load_file() if self.decode else loader.dataset.load_image
         self.slots = loader._slots
         self.order = order
         self.n_batches = -(-len(order) // self.B)
@@ -346,7 +349,8 @@ class DataLoader(object):
         self.dataset, self.batch_size, self.sampler = dataset, int(batch_size), sampler
         self.workers = min(int(workers), MAX_WORKERS)      # a thread count, never sized from the machine
         self.prefetch, self.device_preprocess = int(prefetch), bool(device_preprocess)
-        self.device_decode = bool(device_decode)
+        from .jpeg import decode_switch
+        self.device_decode, self.decode_camera = decode_switch(device_decode)       # (True or 'camera', which also takes 4:2:2 and DRI files)
         if self.device_decode and not (self.device_preprocess and device is not None):
             raise ValueError('device_decode=True needs device_preprocess=True and a device: the decoded images stay on the GPU')
         if self.device_decode and self.batch_size > 32:
@@ -367,7 +371,12 @@ class DataLoader(object):
                 self._transform = dataset.device_transform(self.device)
             if self.device_decode:
                 from .jpeg import DeviceDecodeRoute
-                self._route = DeviceDecodeRoute(self.device)
+                self._route = DeviceDecodeRoute(self.device, self.decode_camera)
+
+    def _load_file(self):
+        """the dataset's ``load_image_file`` with the loader's ``camera`` switch (looked up on the ``device_decode`` routes only)"""
+        load = self.dataset.load_image_file
+        return functools.partial(load, camera=True) if self.decode_camera else load
 
     def __len__(self):
         n = len(self.dataset) if self.sampler is None else len(self.sampler)
@@ -409,7 +418,7 @@ class DataLoader(object):
         B, data = self.batch_size, self.dataset
         for lo in range(0, len(order), B):
             if self.device_preprocess:
-                samples = [draw_train_raw(data, i, None, data.load_image_file if self.device_decode else None) for i in order[lo:lo + B]]
+                samples = [draw_train_raw(data, i, None, self._load_file() if self.device_decode else None) for i in order[lo:lo + B]]
                 if self.device is None:
                     yield samples
                     continue
@@ -493,7 +502,8 @@ def build_dataloader(dataset, imgs_per_gpu, workers_per_gpu, num_gpus=1, dist=Fa
     batch -- with ``device_preprocess=True`` the list of ``prepare_train_raw`` samples ``datasets.collate_device`` takes --;
     ``device='cuda[:n]'`` yields the batch dict on the GPU (``model(**data)``, ``GraphedTrainStep.load``): the ground truth as
     views of ONE uploaded block, ``img`` from ``collate_device`` (one launch) or, on the host route, from the same page-locked
-    block; ``img_meta`` stays a host list.  ``device_decode=True`` (needs ``device_preprocess=True`` and a ``device``, else
+    block; ``img_meta`` stays a host list.  ``device_decode=True`` or ``'camera'`` (the latter also decodes 4:2:2 files and files
+    with restart intervals on the device: ``jpeg.parse_header(camera=True)``; both need ``device_preprocess=True`` and a ``device``, else
     ``ValueError``): the JPEG files are decoded on the GPU too, the same batches bit for bit.  The determinism, lookahead,
     failure and threading contracts: the module docstring."""
     if workers_per_gpu < 0 or prefetch < 0:

@@ -237,28 +237,32 @@ def _test_on(model, dataset, indices, rescale, to_device, imgs_per_gpu=1, device
     prepared ahead in that many threads (``_Prefetched``) and consumed in the same order -- the same calls, the same results.
     ``show``: a ``_Show`` that draws every group's images once its detections exist.  ``device_decode`` (with
     ``device_preprocess``): the samples carry their FILES (``dataset.load_image_file``; the threads only read and parse headers)
-    and every group is decoded on the GPU in one call (``jpeg.DeviceDecodeRoute``) -- the same pixels, the same results."""
+    and every group is decoded on the GPU in one call (``jpeg.DeviceDecodeRoute``) -- the same pixels, the same results; True
+    or 'camera' (4:2:2 files and restart intervals as well, ``jpeg.parse_header(camera=True)``)."""
     if workers < 0:
         raise ValueError('workers is >= 0, got %r' % (workers,))
     if device_decode and not device_preprocess:
         raise ValueError('device_decode=True needs device_preprocess=True: the decoded images stay on the GPU')
     prepare = None
+    from .jpeg import decode_switch
+    device_decode, camera = decode_switch(device_decode)       # (True or 'camera', which also takes 4:2:2 and DRI files)
     if device_decode:
         def prepare(idx):
-            return dataset.prepare_test_raw(idx, img=dataset.load_image_file(idx))
+            return dataset.prepare_test_raw(idx, img=dataset.load_image_file(idx, camera=True) if camera else dataset.load_image_file(idx))
     if workers:
         fn = (prepare or dataset.prepare_test_raw) if device_preprocess else dataset.__getitem__
         ahead = _Prefetched(fn, indices, workers)
         try:
-            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show, prepare)
+            return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show, prepare, camera)
         finally:
             ahead.close()
-    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None, show, prepare)
+    return _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, None, show, prepare, camera)
 
 
-def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show=None, prepare=None):
+def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device_preprocess, sink, ahead, show=None, prepare=None,
+               camera=False):
     if device_preprocess:
-        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead, show, prepare)
+        return _test_on_device(model, dataset, indices, rescale, imgs_per_gpu, sink, ahead, show, prepare, camera)
     model.eval()
     results, i = [], 0
     carried = None                 # the sample that ended the previous group (loaded once)
@@ -296,20 +300,20 @@ def _test_loop(model, dataset, indices, rescale, to_device, imgs_per_gpu, device
     return results
 
 
-def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None, show=None, prepare=None):
+def _test_on_device(model, dataset, indices, rescale, imgs_per_gpu=1, sink=None, ahead=None, show=None, prepare=None, camera=False):
     """``_test_on`` with the input transform on the GPU: samples come from ``dataset.prepare_test_raw`` (raw uint8 pixels +
     planned metas) and go through ``preprocess.DeviceImageTransform`` on the model's device -- one launch per group of
     ``imgs_per_gpu`` single-augmentation samples with the same planned ``pad_shape`` (the grouping of ``_test_on``, whose
     tensor shapes ARE the pad shapes), one launch for all augmentations of a TTA sample (its raw image uploaded once).
     ``prepare``: the ``device_decode`` route's ``prepare_test_raw``, whose ``raw`` is the image's file: the group's files are
-    decoded in one call before the transform."""
+    decoded in one call before the transform (``camera``: by ``kgdet_jpeg_decode_camera``, for files ``prepare`` parsed with that switch)."""
     model.eval()
     device = next(model.parameters()).device
     transform = dataset.device_transform(device)
     route = None
     if prepare is not None:
         from .jpeg import DeviceDecodeRoute
-        route = DeviceDecodeRoute(device)
+        route = DeviceDecodeRoute(device, camera)
     prepare = prepare or dataset.prepare_test_raw
     results, i = [], 0
     carried = None
@@ -418,7 +422,8 @@ def single_gpu_test(model, dataset, rescale=True, to_device=None, imgs_per_gpu=1
     JPEG, quality 90, the bytes of ``jpeg.jpeg_restatement``, not PIL's), only the files come down and the threads only write;
     it takes ``show_ext`` '.jpg' / '.jpeg' (``ValueError`` before the run).  ``device_decode``: the JPEG files are decoded on
     the GPU as well (``jpeg.DeviceDecodeRoute``: every group of the loop in one call, ``workers`` then only read files); it
-    needs ``device_preprocess=True`` (``ValueError`` before the run); same results."""
+    needs ``device_preprocess=True`` (``ValueError`` before the run); same results.  True, or 'camera': 4:2:2 files and files
+    with restart intervals are decoded on the device too instead of by PIL with a warning."""
     if device_decode and not device_preprocess:
         raise ValueError('device_decode=True needs device_preprocess=True: the decoded images stay on the GPU')
     if show_dir is None:
@@ -797,7 +802,7 @@ class Runner(object):
                 results = multi_gpu_test(self.model, dataset, group=group, **kw)
             else:
                 results = single_gpu_test(self.model, dataset, device_results=bool(cfg.get('device_results', False)),
-                                          device_decode=bool(cfg.get('device_decode', False)), **kw)
+                                          device_decode=cfg.get('device_decode', False), **kw)
         finally:
             self.model.train(was_training)
         if results is None:                     # (not rank 0)

@@ -1,7 +1,7 @@
 """Test a detector from a config file and a checkpoint (the reference's ``tools/test.py``), one process on one GPU.
 
     python tools/test.py CONFIG CHECKPOINT [--json_out P] [--eval bbox keypoints] [--workers N] [--imgs-per-gpu N]
-                                           [--device-preprocess [--device-decode]] [--device-results] [--out FILE.pkl]
+                                           [--device-preprocess [--device-decode [--device-decode-files camera]]] [--device-results] [--out FILE.pkl]
                                            [--show-dir DIR] [--show-score-thr T] [--show-encoder {host,device}]
                                            [--grouped-bf16 {0,1,force}]
 
@@ -38,6 +38,9 @@ def parse_args(argv=None):
     parser.add_argument('--device-preprocess', action='store_true')
     parser.add_argument('--device-decode', action='store_true',
                         help='decode the JPEG files on the GPU (needs --device-preprocess)')
+    parser.add_argument('--device-decode-files', choices=('baseline', 'camera'), default='baseline',
+                        help='with --device-decode: which files the GPU decodes; camera adds 4:2:2 files and files with '
+                             'restart intervals, which baseline hands to PIL with a warning')
     parser.add_argument('--device-results', action='store_true')
     parser.add_argument('--out', help='output result file (a pickle of the result list)')
     parser.add_argument('--show-dir', help='directory the drawn images are written to')
@@ -80,7 +83,7 @@ def main(argv=None):
                               imgs_per_gpu=args.imgs_per_gpu, device_preprocess=args.device_preprocess,
                               device_results=args.device_results, workers=min(workers, 16), show_dir=args.show_dir,
                               show_score_thr=args.show_score_thr, show_encoder=args.show_encoder,
-                              device_decode=args.device_decode)
+                              device_decode='camera' if args.device_decode and args.device_decode_files == 'camera' else args.device_decode)
     if args.out:
         import pickle
         print('writing results to {}'.format(args.out))

@@ -1,7 +1,7 @@
 """Train a detector from a config file (the reference's ``tools/train.py``), one process on one GPU.
 
     python tools/train.py CONFIG [--work_dir D] [--resume_from P] [--load_from P] [--validate] [--seed N]
-                                 [--device-preprocess [--device-decode]]
+                                 [--device-preprocess [--device-decode [--device-decode-files camera]]]
 
 CONFIG is one of the reference's config files, unchanged.  ``--device-preprocess`` feeds the raw pixels to the GPU's input
 transform (``loader = dict(device_preprocess=True)``); without it the host pixels go up from page-locked memory.  Checkpoints
@@ -27,6 +27,9 @@ def parse_args(argv=None):
     parser.add_argument('--device-preprocess', action='store_true', help='input transform on the GPU from the raw pixels')
     parser.add_argument('--device-decode', action='store_true',
                         help='decode the JPEG files on the GPU too (needs --device-preprocess)')
+    parser.add_argument('--device-decode-files', choices=('baseline', 'camera'), default='baseline',
+                        help='with --device-decode: which files the GPU decodes; camera adds 4:2:2 files and files with '
+                             'restart intervals, which baseline hands to PIL with a warning')
     parser.add_argument('--launcher', default='none', help='job launcher (only "none")')
     return parser.parse_args(argv)
 
@@ -54,7 +57,7 @@ def main(argv=None):
     if args.device_preprocess:
         cfg.loader = dict(cfg.get('loader') or {}, device_preprocess=True)
     if args.device_decode:
-        cfg.loader = dict(cfg.get('loader') or {}, device_decode=True)
+        cfg.loader = dict(cfg.get('loader') or {}, device_decode='camera' if args.device_decode_files == 'camera' else True)
     cfg.gpus = 1
     if args.seed is not None:
         print('Set random seed to {}'.format(args.seed))
